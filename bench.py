@@ -8,7 +8,11 @@ on pred, gt = (64, 16384, 3) uniform [0,1) clouds per GPU (BASELINE.json
 metric: "point-pairs/sec CD+EMD @2048->16384 pts, batch 64").  Inputs are
 resident in HBM before the timed region.  value = B*N*M*n_gpus / time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload eval|vrcnet_train|pcn_eval]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload eval|vrcnet_train|pcn_eval] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line; everything measured beside the headline (the
+baselines, the roofline and the figures below it that take runs of their own) needs --full.  --dump-outputs DIR writes
+what the last timed step computed as DIR/<name>.npy (inputs are seeded: two builds compare output for output).
 
 N > 1: one rank per GPU over RCCL.  Started by the driver under
 `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` the
@@ -23,21 +27,22 @@ all-reduce of the eval loop.
 --workload vrcnet_train is BASELINE cfg 3 (completion/train.py:122-142 with
 cfgs/vrcnet.yaml): DDP training steps of VRCNet, 32 clouds per rank (global
 batch 32*N), CD loss, Adam; its line reports samples/s, steps/s, the gradient
-all-reduce volume per step and the RCCL bus bandwidth of an all-reduce of that
-volume measured beside the timed region.
+all-reduce volume per step and (--full) the RCCL bus bandwidth of an all-reduce
+of that volume measured beside the timed region and the MFMA roofline.
 
 --workload pcn_eval is BASELINE cfg 2 / SURVEY M6 (completion/test.py:23-64, train.py's val(), models/pcn.py:75-112
 with cfgs/pcn_eval16k.yaml): the eval step of PCN at 2048 -> 16384 points, 32 clouds per rank -- network forward,
-calc_cd with F1 on the network's output, calc_emd at the eval setting -- with per-part milliseconds.
+calc_cd with F1 on the network's output, calc_emd at the eval setting -- with per-part milliseconds (--full).
 
-Rank 0 prints ONE JSON line (contract in the task statement) including
+Rank 0 prints ONE JSON line (metric, value, unit, ms_per_step, ...); with --full it also carries
   roofline     -- for the dominant kernel (the persistent EMD auction kernel)
   cpu_baseline -- the CPU oracle timed on a bounded sample of the same workload
   cpu_baseline_reference_path -- the reference's own CPU path for CD
   gpu_reference_baseline -- the reference's own CD / EMD kernels (oracle/_ref, compiled for gfx950 as written) on the timed batch
                   (distChamfer, restated in metrics/CD/chamfer_python.py) timed
                   with all torch threads
-  extra        -- per-op times, FPS throughput, CD figures.
+  extra        -- per-op times, FPS throughput, the auction statistics, the model-level steps.
+A plain line's `extra` holds the CD / EMD milliseconds of the timed steps and the eval metrics of the last one.
 """
 import argparse
 import json
@@ -68,12 +73,19 @@ def parse():
     ap.add_argument("--points", type=int, default=16384)
     ap.add_argument("--eps", type=float, default=0.004)
     ap.add_argument("--iters", type=int, default=3000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure beside the headline: CPU and reference-kernel baselines, roofline, auction statistics, "
+                         "side and model-level measurements (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU and reference-kernel baselines")
     ap.add_argument("--no-side", action="store_true",
-                    help="skip the untimed side measurements (tools/profile_round.sh: keeps the kernel trace to the headline shape)")
+                    help="with --full: skip the untimed side measurements (tools/profile_round.sh: keeps the kernel trace to the headline shape)")
     ap.add_argument("--cpu-sample", type=int, default=0,
                     help="clouds in the CPU-baseline sample (0 = min(cores, 64))")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.steps is None:
         # (~7 s of timed region for the eval step: long enough for a 5-s utilisation sampler to see it)
         args.steps = 150 if args.workload == "eval" else 50 if args.workload == "pcn_eval" else 10
@@ -247,6 +259,26 @@ def _timeit(fn):
     t0 = time.perf_counter()
     fn()
     return time.perf_counter() - t0
+
+
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: writes `arrays` (name -> tensor, what the last timed step returned) as path/<name>.npy, float64 where
+    the tensor is float64 and float32 otherwise.  An array larger than what is left of the 64 MB budget is replaced by a fixed
+    seeded sample of its elements (flattened, in index order), so two runs with the same arguments write the same files."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > left:
+            idx = np.random.default_rng(0).choice(a.size, left // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def settle(fn, max_steps=200, window=3, tol=0.05):
@@ -506,7 +538,41 @@ def run_eval(args, rank, world, dev):
     if rank != 0:
         return None
 
-    # ---- rank 0 only: side measurements (outside the timed region) ----
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"cd_p": out[0], "cd_t": out[1], "f1": out[2], "emd": out[3]})
+
+    pairs = float(B) * n * n
+    value = pairs * world / (elapsed / args.steps)
+    line = {
+        "metric": "point-pairs/sec CD+EMD @2048->16384 pts, batch 64",
+        "value": value,
+        "unit": "point-pairs/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": "completion eval CD+F1+EMD, pred/gt (%d,%d,3) per GPU, "
+                               "EMD eps=%g iters=%d" % (B, n, args.eps, args.iters),
+                   "batch_per_gpu": B, "points": n, "parallelism": "batch-sharded x%d" % world},
+        "extra": {
+            "cd_f1_ms": cd_ms, "emd_ms": emd_ms,
+            # brute-force-EQUIVALENT rates (all B*N*M pairs / time): the Morton-sorted kernel
+            # evaluates only ~9 % of them, so these are not hardware rates
+            "cd_bruteforce_equivalent_pairs_per_s": 2 * pairs / (cd_ms * 1e-3),
+            "cd_hbm_GBs_20B_per_point": 20.0 * B * 2 * n / (cd_ms * 1e-3) / 1e9,
+            "metrics": {"cd_p": float(sums[0] / sums[4]), "cd_t": float(sums[1] / sums[4]),
+                        "f1": float(sums[2] / sums[4]), "emd": float(sums[3] / sums[4])},
+        },
+    }
+    if not args.full:
+        return line
+
+    # ---- rank 0 only, --full: side measurements (outside the timed region) ----
     # auction statistics of one EMD launch (rounds, bids) via the C ABI
     nbytes = _lib.emd_scratch_bytes(B, n)
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -529,8 +595,6 @@ def run_eval(args, rank, world, dev):
     side = {} if args.no_side else side_measurements(args, dev, g, emd_mod, furthest_point_sample, gather_points,
                                                       reps=3 if world == 1 else 1)
 
-    pairs = float(B) * n * n
-    value = pairs * world / (elapsed / args.steps)
     emd_bytes = 32.0 * B * n  # xyz1+xyz2 in (24 B/pt) + dist+assignment out (8 B/pt)
     achieved = emd_bytes / (emd_ms * 1e-3) / 1e9
     ctr = committed_counters(B, n, args.eps, args.iters)
@@ -548,47 +612,23 @@ def run_eval(args, rank, world, dev):
                  "wait_any_frac": ctr.get("wait_any_frac"), "source": ctr.get("source"),
                  # False: the kernels changed since the committed passes (figures of an older build, kept for the trend)
                  "counters_current": ctr.get("counters_current"), "counters_taken_at": ctr.get("taken_at")}
-    line = {
-        "metric": "point-pairs/sec CD+EMD @2048->16384 pts, batch 64",
-        "value": value,
-        "unit": "point-pairs/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {"workload": "completion eval CD+F1+EMD, pred/gt (%d,%d,3) per GPU, "
-                               "EMD eps=%g iters=%d" % (B, n, args.eps, args.iters),
-                   "batch_per_gpu": B, "points": n, "parallelism": "batch-sharded x%d" % world},
-        # the HBM figures are what the contract asks for; the kernel itself is bound by the
-        # latency of its dependent bid chain, hence bound = "latency" and the
-        # issue-side roof next to it
-        # kernel: one mvp_emd_forward call = emd_auction_kernel (the rounds with four bidders per wave,
-        # ~100 of 3000), emd_lean_kernel (to round 300) and emd_lean_tiers_kernel (the rest, cluster
-        # widths by load); the events bracket the call, the rocprofv3 kernel trace lists the three
-        # durations, whose sum must agree
-        "roofline": {"kernel": "emd_auction_kernel + emd_lean_kernel + emd_lean_tiers_kernel (one mvp_emd_forward)", "bound": "latency", "achieved": achieved,
-                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                     "traffic": traffic, "issue": issue,
-                     "us_per_round": emd_ms * 1e3 / max(rounds, 1)},
-        "extra": {
-            "cd_f1_ms": cd_ms, "emd_ms": emd_ms,
-            "emd_rounds_max": rounds, "emd_bids_per_cloud": bids,
-            "emd_reference_pair_evals_per_s": bids * n * B / (emd_ms * 1e-3),
-            # brute-force-EQUIVALENT rates (all B*N*M pairs / time): the Morton-sorted kernel
-            # evaluates only ~9 % of them, so these are not hardware rates
-            "cd_bruteforce_equivalent_pairs_per_s": 2 * pairs / (cd_ms * 1e-3),
-            "cd_hbm_GBs_20B_per_point": 20.0 * B * 2 * n / (cd_ms * 1e-3) / 1e9,
-            "metrics": {"cd_p": float(sums[0] / sums[4]), "cd_t": float(sums[1] / sums[4]),
-                        "f1": float(sums[2] / sums[4]), "emd": float(sums[3] / sums[4])},
-            "emd_handover": handover,
-            **side,
-        },
-    }
+    # the HBM figures are what the contract asks for; the kernel itself is bound by the
+    # latency of its dependent bid chain, hence bound = "latency" and the
+    # issue-side roof next to it
+    # kernel: one mvp_emd_forward call = emd_auction_kernel (the rounds with four bidders per wave,
+    # ~100 of 3000), emd_lean_kernel (to round 300) and emd_lean_tiers_kernel (the rest, cluster
+    # widths by load); the events bracket the call, the rocprofv3 kernel trace lists the three
+    # durations, whose sum must agree
+    line["roofline"] = {"kernel": "emd_auction_kernel + emd_lean_kernel + emd_lean_tiers_kernel (one mvp_emd_forward)", "bound": "latency", "achieved": achieved,
+                        "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                        "traffic": traffic, "issue": issue,
+                        "us_per_round": emd_ms * 1e3 / max(rounds, 1)}
+    line["extra"].update({
+        "emd_rounds_max": rounds, "emd_bids_per_cloud": bids,
+        "emd_reference_pair_evals_per_s": bids * n * B / (emd_ms * 1e-3),
+        "emd_handover": handover,
+        **side,
+    })
     if world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(args, n)
         line["cpu_baseline_reference_path"] = cpu_reference_path(n)
@@ -654,7 +694,7 @@ def run_vrcnet_train(args, rank, world, dev):
     # gradient all-reduce volume = every parameter that receives a gradient, fp32
     grad_bytes = sum(p.numel() for p in unwrap(net).parameters() if p.grad is not None) * 4
     bus = None
-    if world > 1:
+    if world > 1 and args.full:
         buf = torch.empty(grad_bytes // 4, device=dev)
         for _ in range(2):
             torch.distributed.all_reduce(buf)
@@ -669,7 +709,32 @@ def run_vrcnet_train(args, rank, world, dev):
                "busbw_GBs": grad_bytes / ar / 1e9 * 2 * (world - 1) / world}
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": loss})
     ms = elapsed / args.steps * 1e3
+    line = {
+        "metric": "VRCNet train samples/sec (cfgs/vrcnet.yaml, DDP, batch 32 per GPU)",
+        "value": B * world / (ms * 1e-3),
+        "unit": "samples/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms,
+        "steps_per_s": 1e3 / ms,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": "VRCNet DDP train step (forward, CD losses + KLD, backward, Adam), "
+                               "%d clouds of 2048 pts per GPU" % B,
+                   "global_batch": B * world, "batch_per_gpu": B, "parallelism": "ddp x%d" % world},
+        "grad_allreduce_bytes_per_step": grad_bytes,
+        "rccl": bus,
+        "final_loss": float(loss.mean()),
+    }
+    if not args.full:
+        return line
     # The step's dominant kernels are the float32-MFMA GEMMs of the 1x1 convolutions (csrc/pointwise_mfma.hip,
     # ~10 of the step's ms): their three passes at the step's largest layer, 2 B x (512 -> 1024) x 2048, timed with
     # events on the current stream (after the timed region, 5 repetitions), against the f32 MFMA peak.
@@ -699,28 +764,8 @@ def run_vrcnet_train(args, rank, world, dev):
                 "traffic": None, "per_pass_tflops": passes,
                 "note": "float32 in / float32 accumulate (v_mfma_f32_32x32x2_f32); peak at 2.4 GHz -- the chip holds ~2.05 GHz "
                         "under this load (profiles/r4_pmc_pointwise_512_1024.json)"}
-    return {
-        "metric": "VRCNet train samples/sec (cfgs/vrcnet.yaml, DDP, batch 32 per GPU)",
-        "value": B * world / (ms * 1e-3),
-        "unit": "samples/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms,
-        "steps_per_s": 1e3 / ms,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {"workload": "VRCNet DDP train step (forward, CD losses + KLD, backward, Adam), "
-                               "%d clouds of 2048 pts per GPU" % B,
-                   "global_batch": B * world, "batch_per_gpu": B, "parallelism": "ddp x%d" % world},
-        "grad_allreduce_bytes_per_step": grad_bytes,
-        "rccl": bus,
-        "final_loss": float(loss.mean()),
-        "roofline": roofline,
-    }
+    line["roofline"] = roofline
+    return line
 
 
 def run_pcn_eval(args, rank, world, dev):
@@ -779,6 +824,33 @@ def run_pcn_eval(args, rank, world, dev):
         elapsed = float(t.item())
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict({k: v for k, v in r.items() if torch.is_tensor(v)}, calc_emd=e))
+    mu.check_emd_status()
+    ms = elapsed / args.steps * 1e3
+    line = {
+        "metric": "PCN completion eval clouds/sec (cfgs/pcn_eval16k.yaml: 2048 -> 16384 pts, forward + CD + F1 on the network's "
+                  "output + EMD on a stand-in prediction (chair-like surface, ground truth + noise 0.03), batch 32 per GPU)",
+        "value": B * world / (ms * 1e-3),
+        "unit": "clouds/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms,
+        "steps_per_s": 1e3 / ms,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (random-init PCN weights, uniform clouds; EMD on a surface-shaped pair: prediction = ground truth + noise 0.03)",
+        "config": {"workload": "PCN eval step: forward (2048 -> %d pts) + calc_cd(f1) on its output + calc_emd eps=%g iters=%d, "
+                               "%d clouds per GPU" % (n, args.eps, args.iters, B),
+                   "batch_per_gpu": B, "points": n, "parallelism": "batch-sharded x%d" % world},
+        "extra": {"settled_after_steps": settled,
+                  "metrics": {k: float(r[k].mean()) for k in ("cd_p", "cd_t", "f1")}, "emd_mean": float(e.mean())},
+    }
+    if not args.full:
+        return line
 
     # per-part milliseconds, outside the timed region (events on the current stream, mean of 5)
     def timed(fn, reps=5):
@@ -800,34 +872,14 @@ def run_pcn_eval(args, rank, world, dev):
         surf_ms, _ = timed(lambda: mu.calc_emd(surf_pred, surf_gt, eps=args.eps, iterations=args.iters), reps=3)
         blob_ms, _ = timed(lambda: mu.calc_emd(out2, gt, eps=args.eps, iterations=args.iters), reps=1)
     mu.check_emd_status()
-    ms = elapsed / args.steps * 1e3
-    return {
-        "metric": "PCN completion eval clouds/sec (cfgs/pcn_eval16k.yaml: 2048 -> 16384 pts, forward + CD + F1 on the network's "
-                  "output + EMD on a stand-in prediction (chair-like surface, ground truth + noise 0.03), batch 32 per GPU)",
-        "value": B * world / (ms * 1e-3),
-        "unit": "clouds/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms,
-        "steps_per_s": 1e3 / ms,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic (random-init PCN weights, uniform clouds; EMD on a surface-shaped pair: prediction = ground truth + noise 0.03)",
-        "config": {"workload": "PCN eval step: forward (2048 -> %d pts) + calc_cd(f1) on its output + calc_emd eps=%g iters=%d, "
-                               "%d clouds per GPU" % (n, args.eps, args.iters, B),
-                   "batch_per_gpu": B, "points": n, "parallelism": "batch-sharded x%d" % world},
-        "parts_ms": {"pcn_forward": fwd_ms, "calc_cd_f1_on_network_output": cd_ms, "calc_emd_chair_gt_plus_noise_0.03": surf_ms,
-                     "sum": fwd_ms + cd_ms + surf_ms},
-        "extra": {"settled_after_steps": settled, "calc_emd_independent_uniform_stand_in_ms": emd_ms,
-                  "clouds_per_s_with_emd_on_independent_uniform_stand_in": B * world / ((fwd_ms + cd_ms + emd_ms) * 1e-3),
-                  "calc_emd_on_random_init_output_ms": blob_ms,
-                  "note": "random-init PCN output is one tight blob: the auction against a spread cloud is the degenerate case "
-                          "(every person bids every round); shown for completeness, not part of the timed step",
-                  "metrics": {k: float(r[k].mean()) for k in ("cd_p", "cd_t", "f1")}, "emd_mean": float(e.mean())},
-    }
+    line["parts_ms"] = {"pcn_forward": fwd_ms, "calc_cd_f1_on_network_output": cd_ms, "calc_emd_chair_gt_plus_noise_0.03": surf_ms,
+                        "sum": fwd_ms + cd_ms + surf_ms}
+    line["extra"].update({"calc_emd_independent_uniform_stand_in_ms": emd_ms,
+                          "clouds_per_s_with_emd_on_independent_uniform_stand_in": B * world / ((fwd_ms + cd_ms + emd_ms) * 1e-3),
+                          "calc_emd_on_random_init_output_ms": blob_ms,
+                          "note": "random-init PCN output is one tight blob: the auction against a spread cloud is the degenerate case "
+                                  "(every person bids every round); shown for completeness, not part of the timed step"})
+    return line
 
 
 def main():

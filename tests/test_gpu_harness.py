@@ -978,14 +978,14 @@ def test_conv_max_layer_uses_the_fused_forward_and_matches_autograd():
 
 @pytest.mark.gpu
 def test_bench_line_carries_the_contract_fields(tmp_path):
-    """`python bench.py` on a small shape: ONE JSON line with the driver's contract keys, `roofline`, `cpu_baseline`, and
-    (where oracle/_ref travelled) `gpu_reference_baseline` -- the reference's own kernels on the timed batch."""
+    """`python bench.py --full` on a small shape: ONE JSON line with the driver's contract keys, `roofline`, `cpu_baseline`,
+    and (where oracle/_ref travelled) `gpu_reference_baseline` -- the reference's own kernels on the timed batch."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--batch", "4", "--points", "2048", "--iters", "200",
-                          "--steps", "2", "--warmup", "1", "--cpu-sample", "2", "--no-side"],
+                          "--steps", "2", "--warmup", "1", "--cpu-sample", "2", "--no-side", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -1010,3 +1010,33 @@ def test_bench_line_carries_the_contract_fields(tmp_path):
         assert abs(g["emd_mean_sqrt_dist"] - d["extra"]["metrics"]["emd"]) <= 1e-5 * d["extra"]["metrics"]["emd"], (g, d["extra"]["metrics"])
     else:
         assert g is None
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain `python bench.py` (no --full) times exactly --steps steps and prints the contract keys without the measurements
+    beside the headline; --dump-outputs writes the last timed step's per-cloud results, the same on a second run."""
+    import json
+    import subprocess
+    import sys
+    lines = []
+    for d in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "4", "--points", "2048", "--iters", "200",
+                              "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / d)],
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        rows = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(rows) == 1
+        lines.append(json.loads(rows[0]))
+    d = lines[0]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 4 * 2048 * 2048 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    for key in ("roofline", "cpu_baseline", "cpu_baseline_reference_path", "gpu_reference_baseline"):
+        assert key not in d, key
+    assert "emd_handover" not in d["extra"] and "vrcnet_train_ms" not in d["extra"]
+    for name in ("cd_p", "cd_t", "f1", "emd"):
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.dtype == np.float32 and a.shape == (4,) and np.all(np.isfinite(a))
+        assert np.array_equal(a, b), name
+        assert abs(float(a.mean()) - d["extra"]["metrics"][name]) <= 1e-5 * abs(d["extra"]["metrics"][name]) + 1e-7

@@ -267,3 +267,22 @@ def test_bench_settle_and_model_level_note():
     assert bench.settle(lambda: time.sleep(next(jitter)), max_steps=8) == 8
     note = bench.model_level_note(types.SimpleNamespace(points=16384, eps=0.004, iters=3000))
     assert "5 %" in note and "16384" in note and "0.004 x 3000" in note
+
+
+def test_bench_dump_outputs_budget_and_sample(tmp_path):
+    """bench.py --dump-outputs: float32 (float64 kept), one .npy per output; an array past the 64 MB budget becomes a fixed
+    seeded sample of its elements, the same on every call."""
+    import importlib
+    bench = importlib.import_module("bench")
+    small = torch.arange(6, dtype=torch.float16).view(2, 3)
+    wide = torch.arange(5, dtype=torch.float64)
+    big = torch.arange(bench.DUMP_BUDGET_BYTES // 4 + 1000, dtype=torch.float32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "wide": wide, "big": big})
+    a = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in ("small", "wide", "big")}
+    assert a["small"].dtype == np.float32 and np.array_equal(a["small"], small.float().numpy())
+    assert a["wide"].dtype == np.float64 and np.array_equal(a["wide"], wide.numpy())
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_BUDGET_BYTES
+    assert a["big"].size == (bench.DUMP_BUDGET_BYTES - a["small"].nbytes - a["wide"].nbytes) // 4
+    assert np.all(np.diff(a["big"]) > 0) and np.all(np.isin(a["big"], big.numpy()))
+    assert np.array_equal(a["big"], np.load(tmp_path / "b" / "big.npy"))

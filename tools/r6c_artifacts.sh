@@ -24,7 +24,7 @@ done
 rm -rf $out/pmc_*/
 ls $out; exit 0
 fi
-timeout 900 python bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err; tail -c 200 $out/bench.json
+timeout 900 python bench.py --steps 20 --warmup 5 --full > $out/bench.json 2> $out/bench.err; tail -c 200 $out/bench.json
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o bench -- \
   python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-side > $out/bench_under_rocprof.json 2> $out/trace.err
 find $out/trace -name "*kernel_stats.csv" -exec cp {} $out/bench_kernel_stats.csv \; ; rm -rf $out/trace
@@ -34,5 +34,5 @@ find $out/trace -name "*kernel_stats.csv" -exec cp {} $out/bench_kernel_stats.cs
   MVP_BENCH_REPS=5 timeout 300 python tools/bench_emd_one.py 64 2048 0.005 50; } > $out/bench_emd_sweep.txt 2>&1
 timeout 900 python tools/emd_surfaces.py 64 16384 > $out/emd_surfaces_16384.txt 2>&1
 timeout 600 python tools/emd_surfaces.py 64 2048 > $out/emd_surfaces_2048.txt 2>&1
-timeout 600 python bench.py --workload pcn_eval --steps 20 --warmup 3 > $out/bench_pcn_eval.json 2>> $out/bench.err
+timeout 600 python bench.py --workload pcn_eval --steps 20 --warmup 3 --full > $out/bench_pcn_eval.json 2>> $out/bench.err
 ls $out
