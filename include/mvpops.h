@@ -43,7 +43,7 @@ extern "C" {
 #define MVP_ELAUNCH (-3)
 
 /* ABI version of this header; bumped on any signature change. */
-#define MVP_ABI_VERSION 18
+#define MVP_ABI_VERSION 19
 int mvp_abi_version(void);
 
 /* hipGetErrorString of the last launch failure seen on the calling thread
@@ -550,6 +550,45 @@ int mvp_pointwise_max_backward(int b, int cin, int cout, int len, const float *x
  * One-sided Jacobi in float64 per matrix, outputs rounded to float32. */
 int mvp_kabsch_svd3(int b, const float *H, float *R, float *U, float *S,
                     float *V, int *flipped, void *stream);
+
+/* ------------------------------------------- registration (DeepGMR) head */
+
+/* Replaces get_rri_cluster's feature computation (registration/models/deepgmr.py:54-96):
+ * rp, rq, theta in torch, then T_q and p/|p| copied to the host and the (B*M, S, k, k, 3)
+ * np.cross / np.sum / np.arctan2 / np.argpartition temporaries there.
+ * xyz (b,n,3), idx (b,n,k) int32 = the k neighbours of every point, self column already
+ * dropped (knn(pts, k+1)[:, :, 1:]), each in [0, n) -> feat (b,4k,n): channel 4a+f holds
+ * f in {rp = |p|, rq = |q_a|, theta = acos(clamp(p^.q^_a, -1, 1)), phi} of neighbour slot a,
+ * the layout of the reference's cat(...).view(B,M,S,4k).transpose(1,3).  phi_a is the second
+ * smallest of the multiset psi[a, 0..k-1] (psi[a,a] = 0 included), psi[a,b] =
+ * remainder(atan2((T_b x T_a).p^, T_b.T_a), 2 pi) in float32, T_a = q_a - (p^.q^_a) p with the
+ * unclamped dot.  2 <= k <= 64 (k < 2 -> MVP_EBADARG: the reference's argpartition fails).
+ * Forward only: the reference's phi goes through NumPy, no gradient reaches xyz. */
+int mvp_rri_features(int b, int n, int k, const float *xyz, const int *idx, float *feat,
+                     void *stream);
+
+/* Replaces gmm_params (registration/models/deepgmr.py:98-121) and the softmax in front of it
+ * (Model.forward :231-234: F.softmax(backbone(feats), dim=2)).
+ * logits (b,j,n) = the backbone's last 1x1 convolution as it comes (no transposed copy) ->
+ * gamma (b,n,j) = softmax over j (max-subtracted); pi (b,j) = mean_n gamma;
+ * mu (b,j,3) = sum_n gamma p / (N pi); sigma (b,j) = the isotropic variance
+ * sum_n gamma |p - mu|^2 / (N pi), two-pass (the reference's (b,j,3,3) is sigma * I).
+ * 1 <= j <= 64 (else MVP_EBADARG), n >= 1.  Fixed summation orders, no atomics:
+ * bit-reproducible. */
+int mvp_gmm_params(int b, int n, int j, const float *logits, const float *xyz, float *gamma,
+                   float *pi, float *mu, float *sigma, void *stream);
+
+/* Backward of mvp_gmm_params with respect to the logits (no gradient to xyz):
+ *   g_gamma[n][j] = g_pi_j / N + g_mu_j . (p_n - mu_j) / (N pi_j)
+ *                   + g_sigma_j (|p_n - mu_j|^2 - sigma_j) / (N pi_j)
+ * (sigma's dependence on mu drops out: sum_n gamma_nj (p_n - mu_j) = 0), then the softmax
+ *   g_logits[j][n] = gamma_nj (g_gamma[n][j] - sum_j' gamma_nj' g_gamma[n][j']).
+ * gamma, pi, mu, sigma: the forward's outputs; g_pi (b,j), g_mu (b,j,3), g_sigma (b,j) (all
+ * required; pass zeros for an unused output) -> g_logits (b,j,n), every entry written. */
+int mvp_gmm_params_backward(int b, int n, int j, const float *gamma, const float *xyz,
+                            const float *pi, const float *mu, const float *sigma,
+                            const float *g_pi, const float *g_mu, const float *g_sigma,
+                            float *g_logits, void *stream);
 
 #ifdef __cplusplus
 }

@@ -58,11 +58,14 @@ SIGNATURES = {
     "mvp_pointwise_wgrad_mfma_ex": "iiiipipppppq",
     "mvp_pointwise_max_backward": "iiiippppppppq",
     "mvp_pointwise_mfma_max": "iiiippipipppq",
+    "mvp_rri_features": "iiippp",
+    "mvp_gmm_params": "iiipppppp",
+    "mvp_gmm_params_backward": "iiippppppppp",
 }
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "f": ctypes.c_float,
        "q": ctypes.c_longlong}
 
-ABI_VERSION = 18  # MVP_ABI_VERSION of include/mvpops.h this binding was written against
+ABI_VERSION = 19  # MVP_ABI_VERSION of include/mvpops.h this binding was written against
 
 # default of mvp_emd_configure's `split` knob (csrc/emd.hip: emd_knobs)
 EMD_DEFAULT_SPLIT = 5

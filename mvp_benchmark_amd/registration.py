@@ -13,7 +13,11 @@ the backward pass is the closed-form SVD adjoint on (B,3,3) tensors (batched
 elementwise / 3x3 matmul PyTorch ops, device-agnostic, no loop, no sync) -- the
 same gradient torch.svd's autograd produces for R = V D U^T with the reflection
 D held fixed.
+
+The DeepGMR pieces (rri_features, gmm_params, gmm_register) follow at the end.
 """
+import math
+
 import torch
 from torch.autograd import Function
 
@@ -84,3 +88,160 @@ def svd3(H):
     flipped = torch.empty(b, device=H.device, dtype=torch.int32)
     call("mvp_kabsch_svd3", H.device, b, H, R, U, S, V, flipped)
     return U, S, V, R, flipped
+
+
+# ---------------------------------------------------------------------------------------------------- DeepGMR
+# registration/models/deepgmr.py's two op-layer pieces: the RRI features of every point and the moments of the soft
+# Gaussian mixture (mvp_rri_features, mvp_gmm_params[_backward]); gmm_register closes the loop with kabsch_rotation.
+# float32 CUDA tensors run the kernels; CPU / float64 tensors take the reference's formulation written in torch (the
+# float64 equivalence tests run on it).
+
+def _on_op_layer(t):
+    return t.is_cuda and t.dtype == torch.float32
+
+
+def _knn_reference(xyz, k):
+    """(B,N,3) -> (B,N,k) int64: topk of the negated expanded squared distance (deepgmr.py:10-15), self included."""
+    inner = -2 * xyz @ xyz.transpose(1, 2)
+    xx = (xyz * xyz).sum(dim=2, keepdim=True)
+    return (-xx - inner - xx.transpose(1, 2)).topk(k=k, dim=-1)[1]
+
+
+def _rri_reference(xyz, idx):
+    """get_rri_cluster (deepgmr.py:54-96) in torch, one cloud at a time so the (N,k,k,3) temporaries stay per cloud:
+    xyz (B,N,3), idx (B,N,k) -> (B,4k,N).  phi = the second smallest psi of each row (np.argpartition(psi, 1))."""
+    B, N, k = idx.shape
+    out = []
+    for b in range(B):
+        p = xyz[b].unsqueeze(1).expand(N, k, 3)
+        q = xyz[b][idx[b]]                                        # (N,k,3)
+        rp = torch.norm(p, dim=-1, keepdim=True)
+        rq = torch.norm(q, dim=-1, keepdim=True)
+        pn = p / rp
+        dot = (pn * (q / rq)).sum(dim=-1, keepdim=True)
+        theta = torch.acos(dot.clamp(-1, 1))
+        T = q - dot * p
+        # [i, a, b]: sin = (T_b x T_a) . p^, cos = T_b . T_a (np.cross(T_q[:, :, None], T_q[:, :, :, None]))
+        # (the cross product spelled out like np.cross: torch.linalg.cross may contract into fmas, and then
+        # T_a x T_a is not exactly 0 and psi[a, a] leaves the multiset's bottom)
+        Tb, Ta = T.unsqueeze(1), T.unsqueeze(2)
+        cross = torch.stack([Tb[..., 1] * Ta[..., 2] - Tb[..., 2] * Ta[..., 1],
+                             Tb[..., 2] * Ta[..., 0] - Tb[..., 0] * Ta[..., 2],
+                             Tb[..., 0] * Ta[..., 1] - Tb[..., 1] * Ta[..., 0]], dim=-1)
+        sin_psi = (cross * pn.unsqueeze(1)).sum(dim=-1)
+        cos_psi = (Tb * Ta).sum(dim=-1)
+        psi = torch.remainder(torch.atan2(sin_psi, cos_psi), 2 * math.pi)
+        phi = psi.sort(dim=-1).values[:, :, 1:2]
+        out.append(torch.cat([rp, rq, theta, phi], dim=-1).reshape(N, 4 * k).t())
+    return torch.stack(out)
+
+
+def rri_features(xyz, k):
+    """Rotation-reference-invariant features of every point (get_rri_cluster, deepgmr.py:54-96, with one cluster):
+    xyz (B,N,3) -> (B,4k,N), channel 4a+f = {rp, rq, theta, phi}[f] of neighbour slot a.  Returned detached: the
+    reference's phi goes through NumPy, so no gradient ever reaches the points.
+
+    Neighbours: the knn operator with k+1, first slot dropped.  It stands in for the reference's topk of the expanded
+    distance (deepgmr.py:10-15); the two agree except where rounding ties two distances, exactly as for DCP's graph.
+    With duplicate points, self and its duplicate are interchangeable (same coordinates): the features come out the
+    same whichever of the two is dropped."""
+    xyz = xyz.detach()
+    if _on_op_layer(xyz):
+        from .mm3d_pn2 import knn
+        xyz = xyz.contiguous()
+        B, N, _ = xyz.shape
+        idx = knn(k + 1, xyz)[:, 1:, :].transpose(1, 2).contiguous()     # (B,k+1,N) -> (B,N,k) int32
+        feat = torch.empty(B, 4 * k, N, device=xyz.device, dtype=torch.float32)
+        call("mvp_rri_features", xyz.device, B, N, k, xyz, idx, feat)
+        return feat
+    if k < 2:
+        raise ValueError("rri_features needs k >= 2 (got %d)" % k)
+    return _rri_reference(xyz, _knn_reference(xyz, k + 1)[:, :, 1:])
+
+
+def _gmm_params_reference(logits, xyz):
+    """gamma = softmax over the components, then gmm_params (deepgmr.py:98-121) with the isotropic variance kept as
+    (B,J) (the reference's (B,J,3,3) is sigma * I)."""
+    gamma = torch.softmax(logits.transpose(1, 2), dim=2)         # (B,N,J)
+    pi = gamma.mean(dim=1)
+    npi = pi * gamma.shape[1]
+    mu = gamma.transpose(1, 2) @ xyz / npi.unsqueeze(2)
+    diff = xyz.unsqueeze(2) - mu.unsqueeze(1)                    # (B,N,J,3)
+    sigma = ((diff * diff).sum(dim=3) * gamma).sum(dim=1) / npi
+    return gamma, pi, mu, sigma
+
+
+def gmm_params_backward_reference(gamma, xyz, pi, mu, sigma, g_pi, g_mu, g_sigma):
+    """The closed form mvp_gmm_params_backward computes, in torch: -> g_logits (B,J,N)."""
+    n = gamma.shape[1]
+    npi = (pi * n).unsqueeze(1)                                  # (B,1,J)
+    diff = xyz.unsqueeze(2) - mu.unsqueeze(1)                    # (B,N,J,3)
+    g_gamma = (g_pi.unsqueeze(1) / n + (diff * g_mu.unsqueeze(1)).sum(dim=3) / npi
+               + g_sigma.unsqueeze(1) * ((diff * diff).sum(dim=3) - sigma.unsqueeze(1)) / npi)
+    g_logits = gamma * (g_gamma - (gamma * g_gamma).sum(dim=2, keepdim=True))
+    return g_logits.transpose(1, 2)
+
+
+class GmmParams(Function):
+    """(logits (B,J,N), xyz (B,N,3)) -> gamma (B,N,J), pi (B,J), mu (B,J,3), sigma (B,J).  Gradient to the logits
+    only (through pi, mu and sigma; gamma itself is returned without a gradient path, none of the model's losses
+    reads it); none to xyz, whose coordinates never require grad in the reference."""
+
+    @staticmethod
+    def forward(ctx, logits, xyz):
+        assert logits.dim() == 3 and xyz.dim() == 3 and xyz.shape[2] == 3
+        assert logits.shape[0] == xyz.shape[0] and logits.shape[2] == xyz.shape[1]
+        if _on_op_layer(logits):
+            logits, xyz = logits.contiguous(), xyz.detach().float().contiguous()
+            B, J, N = logits.shape
+            gamma = torch.empty(B, N, J, device=logits.device, dtype=torch.float32)
+            pi = torch.empty(B, J, device=logits.device, dtype=torch.float32)
+            mu = torch.empty(B, J, 3, device=logits.device, dtype=torch.float32)
+            sigma = torch.empty(B, J, device=logits.device, dtype=torch.float32)
+            call("mvp_gmm_params", logits.device, B, N, J, logits, xyz, gamma, pi, mu, sigma)
+        else:
+            xyz = xyz.detach().to(logits.dtype)
+            gamma, pi, mu, sigma = _gmm_params_reference(logits, xyz)
+        ctx.save_for_backward(gamma, xyz, pi, mu, sigma)
+        ctx.mark_non_differentiable(gamma)
+        return gamma, pi, mu, sigma
+
+    @staticmethod
+    def backward(ctx, _g_gamma, g_pi, g_mu, g_sigma):
+        gamma, xyz, pi, mu, sigma = ctx.saved_tensors
+        if not _on_op_layer(gamma):
+            return gmm_params_backward_reference(gamma, xyz, pi, mu, sigma, g_pi, g_mu, g_sigma), None
+        B, N, J = gamma.shape
+        g_logits = torch.empty(B, J, N, device=gamma.device, dtype=torch.float32)
+        call("mvp_gmm_params_backward", gamma.device, B, N, J, gamma, xyz, pi, mu, sigma,
+             g_pi.float().contiguous(), g_mu.float().contiguous(), g_sigma.float().contiguous(), g_logits)
+        return g_logits, None
+
+
+def gmm_params(logits, xyz):
+    """Soft assignment and mixture moments of one cloud batch (DeepGMR's softmax + gmm_params): see GmmParams."""
+    return GmmParams.apply(logits, xyz)
+
+
+def _kabsch_reference(H):
+    """R = V diag(1, 1, det(V U^T)) U^T of H = U S V^T in torch (gmm_register's torch.svd + determinant)."""
+    U, _, Vh = torch.linalg.svd(H)
+    V = Vh.transpose(1, 2)
+    d = torch.ones(H.shape[0], 3, dtype=H.dtype, device=H.device)
+    d[:, 2] = torch.where(torch.linalg.det(V @ U.transpose(1, 2)) < 0, -1.0, 1.0).to(H.dtype)
+    return (V * d.unsqueeze(1)) @ U.transpose(1, 2)
+
+
+def gmm_register(pi_s, mu_s, mu_t, sigma_t):
+    """Closed-form rigid motion between two mixtures (gmm_register, deepgmr.py:123-144): pi_s (B,J), mu_s / mu_t
+    (B,J,3), sigma_t (B,J) isotropic variances -> T (B,4,4) taking the source onto the target.
+      c_s = pi_s mu_s, c_t = pi_s mu_t, Ms = sum_j pi_j (mu_s_j - c_s)(mu_t_j - c_t)^T / sigma_t_j
+    (sigma_t is sigma * I: no 3x3 inverse), R = kabsch_rotation(Ms) (one mvp_kabsch_svd3 launch in place of a
+    host-side torch.svd and a determinant), t = c_t - R c_s."""
+    c_s = pi_s.unsqueeze(1) @ mu_s                               # (B,1,3)
+    c_t = pi_s.unsqueeze(1) @ mu_t
+    Ms = ((pi_s.unsqueeze(2) * (mu_s - c_s)) / sigma_t.unsqueeze(2)).transpose(1, 2) @ (mu_t - c_t)
+    R = kabsch_rotation(Ms) if _on_op_layer(Ms) else _kabsch_reference(Ms)
+    t = c_t.transpose(1, 2) - R @ c_s.transpose(1, 2)
+    bottom = R.new_tensor([0.0, 0.0, 0.0, 1.0]).expand(R.shape[0], 1, 4)
+    return torch.cat([torch.cat([R, t], dim=2), bottom], dim=1)
