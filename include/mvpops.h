@@ -563,6 +563,11 @@ int mvp_kabsch_svd3(int b, const float *H, float *R, float *U, float *S,
  * smallest of the multiset psi[a, 0..k-1] (psi[a,a] = 0 included), psi[a,b] =
  * remainder(atan2((T_b x T_a).p^, T_b.T_a), 2 pi) in float32, T_a = q_a - (p^.q^_a) p with the
  * unclamped dot.  2 <= k <= 64 (k < 2 -> MVP_EBADARG: the reference's argpartition fails).
+ * Non-finite inputs: a point at the origin has no direction, so theta and phi of all its slots
+ * are NaN; a neighbour at the origin makes theta and phi of that one slot NaN and takes no part
+ * in the phi of the point's other slots (the clamp keeps a NaN, and phi is NaN where a row holds
+ * fewer than two non-NaN psi), as the reference's clamp and NaN-last sort.  rp and rq stay
+ * finite.  Never pi or inf in their place: a zero-padded cloud shows as NaN.
  * Forward only: the reference's phi goes through NumPy, no gradient reaches xyz. */
 int mvp_rri_features(int b, int n, int k, const float *xyz, const int *idx, float *feat,
                      void *stream);

@@ -9,7 +9,8 @@
 // [slot][component][lane] (k * 3 * 64 floats of dynamic LDS: 15 KiB at k = 20, 48 KiB at k = 64).  Phase 2: each
 // (point, slot a) walks all k slots b, reading T_b from LDS (lane-contiguous: conflict-free), and keeps the two
 // smallest psi[a, b] -- phi_a is the second smallest of that multiset, psi[a, a] = 0 included
-// (np.argpartition(psi, 1)[..., 1]).  k^2 atan2 per point.
+// (np.argpartition(psi, 1)[..., 1]).  k^2 atan2 per point.  A point at the origin (|p| = 0) or a neighbour there
+// (|q_a| = 0) has no direction: theta and phi of the affected slots are NaN, as in the reference (see mvpops.h).
 //
 // GMM moments (replace gmm_params, deepgmr.py:98-121, and the softmax of Model.forward, :231-234).  Two launches
 // for the forward pass: the softmax over j per point (grid over n-chunks x clouds), then one workgroup per
@@ -53,7 +54,9 @@ __global__ __launch_bounds__(kWave *kRriWaves) void rri_features_kernel(int n, i
     const float qx = pts[j * 3 + 0], qy = pts[j * 3 + 1], qz = pts[j * 3 + 2];
     const float rq = sqrtf(dot3(qx, qy, qz, qx, qy, qz));
     const float d = dot3(pnx, pny, pnz, qx / rq, qy / rq, qz / rq);
-    const float theta = acosf(fminf(fmaxf(d, -1.0f), 1.0f));
+    // clamp that keeps a NaN (fmaxf / fminf return their non-NaN operand and would turn it into acos(-1) = pi):
+    // a point or a neighbour at the origin has no direction, theta is NaN as in the reference's torch.clamp
+    const float theta = acosf(d < -1.0f ? -1.0f : d > 1.0f ? 1.0f : d);
     // T_a = q - (p^ . q^) p: the unclamped dot and the unnormalised p, as the reference writes it
     T[(a * 3 + 0) * kWave + lane] = qx - d * px;
     T[(a * 3 + 1) * kWave + lane] = qy - d * py;
@@ -88,7 +91,9 @@ __global__ __launch_bounds__(kWave *kRriWaves) void rri_features_kernel(int n, i
         m2 = psi;
       }
     }
-    if (valid) out[(size_t)(4 * a + 3) * n] = m2;
+    // every finite psi is <= 2 pi, so m2 is still +inf only when the row holds fewer than two non-NaN psi (the
+    // point or all but one tangent undefined): NaN, as the reference's sort, which puts NaN last
+    if (valid) out[(size_t)(4 * a + 3) * n] = m2 == INFINITY ? NAN : m2;
   }
 }
 

@@ -7,7 +7,10 @@ Stored: parameter names + shapes of registration/models/deepgmr.py:Model at the 
 (2, 256, 3) and T_gt; the reference's RRI features of the first cloud batch for
 k = 20 and k = 5 (get_rri_cluster, one cluster); softmax + gmm_params for fixed
 logits (sigma as its isotropic diagonal); and the model's outputs in eval mode on
-CPU: T_12 and (loss, r_err, t_err, rmse, mse).  Parameters are filled with
+CPU: T_12 and (loss, r_err, t_err, rmse, mse); the same six outputs of the two
+variants without RRI (raw centred coordinates into the backbone), `norri_*` for
+use_rri=False and `norri_tnet_*` for use_rri=False + use_tnet=True (the T-net takes
+3 channels, so it excludes RRI).  Parameters are filled with
 make_dcp_golden.fill_parameters on both sides.  B = 2: the reference's `.squeeze()`
 in gmm_params drops a batch of one.
 
@@ -89,6 +92,15 @@ def main():
         out["T_12"] = net(pts1, pts2, prefix="test").numpy()
         loss, r_err, t_err, rmse, mse = net(pts1, pts2, T_gt, prefix="val")
     out.update(loss=loss.numpy(), r_err=r_err.numpy(), t_err=t_err.numpy(), rmse=rmse.numpy(), mse=mse.numpy())
+    with torch.no_grad():
+        for key, over in (("norri_", dict(use_rri=False)), ("norri_tnet_", dict(use_rri=False, use_tnet=True))):
+            var = deepgmr.Model(types.SimpleNamespace(**dict(ARGS, **over)))
+            fill_parameters(var)
+            var.eval()
+            out[key + "T_12"] = var(pts1, pts2, prefix="test").numpy()
+            vals = var(pts1, pts2, T_gt, prefix="val")
+            for name, v in zip(("loss", "r_err", "t_err", "rmse", "mse"), vals):
+                out[key + name] = v.numpy()
     np.savez_compressed(OUT, **out)
     print("wrote", OUT, os.path.getsize(OUT), "bytes; params", sum(p.numel() for p in net.parameters()))
     print("T_12[0]", out["T_12"][0], "loss", loss, "r_err", r_err, "t_err", t_err)
