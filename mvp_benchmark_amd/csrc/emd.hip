@@ -67,6 +67,7 @@
 
 #include "emd_common.h"
 #include "emd_index.h"
+#include "emd_probe.h"
 
 namespace mvp {
 
@@ -87,9 +88,7 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
   if (cloud >= b) return;
   char *cbase = scratch + (size_t)cloud * emd_scratch_per_cloud(n);
   char *tail = scratch + (size_t)b * emd_scratch_per_cloud(n);
-#ifdef MVP_EMD_CLOUDTIME
-  const long long ct_a0 = wall_clock64();
-#endif
+  EMD_CTIME(const long long ct_a0 = wall_clock64();)
   u64 *slots = emd_granules(tail, b, cloud, 0);
   // per-cloud auction statistics {rounds executed, bids made} (read by
   // bench.py; not part of the op's result)
@@ -104,80 +103,11 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
   int *ass = assignment + (size_t)cloud * n;
   const EmdScratch sc = emd_carve(cbase, n);
 
-  // ---- accessors of the shared auction state.  W == 1: plain.  W > 1: loads
-  // bypass this CU's L1 (sc1), stores are written through (sc1), so data is
-  // visible to the other workgroups once the store is acknowledged.
+  // ---- accessors of the shared auction state (emd_common.h): sa.ld_obj(slot), sa.st_ostate(slot, owner), ...
+  // same_xcd is set below, after the cluster's first gather; the accessors read it through a reference.
   const auto rs = __builtin_amdgcn_make_buffer_rsrc(cbase, 0, (int)emd_scratch_per_cloud(n), 0x00020000);
-  auto ld_obj = [&](int s) -> float4 {
-    if constexpr (W == 1) {
-      return sc.obj[s];
-    } else {
-      const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rs, (unsigned)s * 16u, 0, 16);
-      return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-    }
-  };
-  auto ld_price = [&](int s) -> float {  // obj[s].w alone
-    if constexpr (W == 1) return sc.obj[s].w;
-    else return __uint_as_float((unsigned)__builtin_amdgcn_raw_buffer_load_b32(rs, (unsigned)s * 16u + 12u, 0, 16));
-  };
-  auto ld_ostate = [&](int s) -> int4 {
-    if constexpr (W == 1) {
-      return sc.ostate[s];
-    } else {
-      const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rs, ((unsigned)n + (unsigned)s) * 16u, 0, 16);
-      return make_int4((int)v.x, (int)v.y, (int)v.z, (int)v.w);
-    }
-  };
-  auto ld_person = [&](int j, int half) -> float4 {  // half 0 = lo, 1 = hi
-    if constexpr (W == 1) {
-      return sc.person[2 * j + half];
-    } else {
-      const v4u v =
-          __builtin_amdgcn_raw_buffer_load_b128(rs, (2u * (unsigned)n + 2u * (unsigned)j + (unsigned)half) * 16u, 0, 16);
-      return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-    }
-  };
-  // Stores of shared words.  When every member of the cluster was observed on
-  // the same XCD (same_xcd, below) they share one L2, the coherence point of
-  // that XCD's CUs: a plain store (L1 is write-through) is visible to the
-  // others' L1-bypassing loads as soon as it is acknowledged, and the line
-  // stays in L2 instead of being written through to memory and dropped.
   bool same_xcd = false;
-  auto st_person_hi = [&](int j, int bid, int p1, int p2, float inc) {
-    if constexpr (W == 1) {
-      sc.person[2 * j + 1] = make_float4(__int_as_float(bid), __int_as_float(p1), __int_as_float(p2), inc);
-    } else {
-      v4u v;
-      v.x = (unsigned)bid; v.y = (unsigned)p1; v.z = (unsigned)p2; v.w = __float_as_uint(inc);
-      if (same_xcd) __builtin_amdgcn_raw_buffer_store_b128(v, rs, (2u * (unsigned)n + 2u * (unsigned)j + 1u) * 16u, 0, 0);
-      else __builtin_amdgcn_raw_buffer_store_b128(v, rs, (2u * (unsigned)n + 2u * (unsigned)j + 1u) * 16u, 0, 16);
-    }
-  };
-  auto st_ostate = [&](int s, int owner) {  // key = 0 (no bid), new owner
-    if constexpr (W == 1) {
-      sc.ostate[s] = make_int4(0, 0, owner, 0);
-    } else {
-      v4u v;
-      v.x = 0u; v.y = 0u; v.z = (unsigned)owner; v.w = 0u;
-      if (same_xcd) __builtin_amdgcn_raw_buffer_store_b128(v, rs, ((unsigned)n + (unsigned)s) * 16u, 0, 0);
-      else __builtin_amdgcn_raw_buffer_store_b128(v, rs, ((unsigned)n + (unsigned)s) * 16u, 0, 16);
-    }
-  };
-  auto st_i32 = [&](int *p, int v) {
-    if constexpr (W == 1) *p = v;
-    else if (same_xcd) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
-  auto st_f32 = [&](float *p, float v) {
-    if constexpr (W == 1) *p = v;
-    else if (same_xcd) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
-  auto ld_key = [&](int s) -> u64 {
-    u64 *p = reinterpret_cast<u64 *>(&sc.ostate[s]);
-    if constexpr (W == 1) return *p;
-    else return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
+  const EmdShared<W> sa{rs, sc, n, same_xcd};
 
   // The index (emd_index.h): per leaf and per node {box min x, y, z, price lower bound} and {box max x, y, z, -}:
   // a box test is two ds_read_b128 per lane.  (During the build the leaves' 32 KB hold the sort's 512 x 16 counters.)
@@ -193,15 +123,7 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
   __shared__ int s_err, s_abort, s_nchg, s_xcc;
   __shared__ int s_alarm[2];  // by round parity: set in Bid, read after the barrier, cleared a round later
   __shared__ unsigned s_gout[2 * kMaxCluster];
-#ifdef MVP_EMD_PROFILE
-  __shared__ int s_wbusy[kEmdWaves];
-  __shared__ unsigned long long s_hist2[4];
-  if (threadIdx.x < 4) s_hist2[threadIdx.x] = 0;
-  __shared__ unsigned long long s_slow[2][8];  // [d >= 10k cycles][count, nsub, cells, visit steps, extra member iterations, folds, seed cycles, visit cycles]
-  if (threadIdx.x < 16) s_slow[threadIdx.x >> 3][threadIdx.x & 7] = 0;
-  __shared__ unsigned long long s_hist[16];  // wave-mode bids: [0..7] duration buckets, [8] sum nsub, [9] sum cells visited, [10] count, [11] linear scans, [12] sum cycles
-  if (threadIdx.x < 16) s_hist[threadIdx.x] = 0;
-#endif
+  EMD_PROF(__shared__ EmdProbeLds pl; pl.clear();)
   // this round's bids for the first kBidCache list positions (skips two
   // dependent global round trips in Assign)
   __shared__ int s_bj[kBidCache], s_bo[kBidCache], s_b2k[kBidCache];
@@ -365,19 +287,10 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
   // would only add latency: member 0 adopts the others' lists and carries on
   // alone (same code, workgroup barriers), the others leave.
   bool clustered = W > 1;
-#ifdef MVP_EMD_PROFILE
-  long long prof_pg1 = 0, prof_drain = 0, prof_gather = 0, cyc_bid = 0, cyc_sync1 = 0, cyc_assign = 0, cyc_sync2 = 0, n_alarm = 0, n_rebal = 0, prof_u = 0, prof_a1 = 0, prof_an = 0, prof_a2 = 0, prof_a3 = 0, prof_a4 = 0;
-#endif
-#ifdef MVP_EMD_PROFILE
-  const long long t_loop0 = __builtin_readcyclecounter();
-#endif
+  EMD_PROF(EmdProbe pr;)
   for (int it = 0; it < iters; ++it) {
     if (Utot == 0) break;
-#ifdef MVP_EMD_PROFILE
-    if (cloud == 0 && wg == 0 && t == 0 && (it == 1 || it == 2 || it == 3 || it == 5 || it == 10 || it == 25 || it == 50 || it == 100 || it == 150 || it == 250 || it == 500 || it == 750 ||
-                                           it == 1000 || it == 1500 || it == 2000 || it == 2500 || it == iters - 1))
-      printf("head cloud 0: round %d starts at %lld cycles, unassigned %d\n", it, __builtin_readcyclecounter() - t_loop0, Utot);
-#endif
+    EMD_PROF(pr.head(true, cloud, wg, it, iters, Utot);)
     const int U = s_cnt[cur];  // this workgroup's bidders
     n_rounds += 1;
     n_bids += U;
@@ -389,9 +302,7 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
     const int upb = (Utot + block_cnt - 1) / block_cnt;
     const int tpu = 1024 / upb;
 
-#ifdef MVP_EMD_PROFILE
-    const long long tp0 = __builtin_readcyclecounter();
-#endif
+    EMD_PROF(const long long tp0 = __builtin_readcyclecounter();)
     // A bid = one returning 64-bit atomic max on the object's key; the value
     // it returns is examined one bid later (or after the loop), so the wave
     // never waits for it.
@@ -422,8 +333,8 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
             rb = s_ri[cur][u];
           } else {
             const int jj = L[u];
-            ra = ld_person(jj, 0);
-            const float4 g = ld_person(jj, 1);
+            ra = sa.ld_person(jj, 0);
+            const float4 g = sa.ld_person(jj, 1);
             rb = make_int4(jj, __float_as_int(g.y), __float_as_int(g.z), 0);
           }
         }
@@ -443,9 +354,9 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
           const bool hint = act && ((l16 == 0 && p1 >= 0 && (p1 >> 4) != hc) || (l16 == 1 && p2 >= 0 && (p2 >> 4) != hc));
           const bool two = act && p1 < 0 && p2 < 0;   // row-uniform
           float4 oh = make_float4(0.f, 0.f, 0.f, 0.f), o0 = oh, o1 = oh;
-          if (hint) oh = ld_obj(l16 == 0 ? p1 : p2);
-          if (act) o0 = ld_obj(hc * 16 + l16);
-          if (two) o1 = ld_obj((hc ^ 1) * 16 + l16);
+          if (hint) oh = sa.ld_obj(l16 == 0 ? p1 : p2);
+          if (act) o0 = sa.ld_obj(hc * 16 + l16);
+          if (two) o1 = sa.ld_obj((hc ^ 1) * 16 + l16);
           if (act) top2_insert(a1, a2, emd_value(sqdist3(o0.x - qx, o0.y - qy, o0.z - qz), o0.w));
           if (two) top2_insert(a1, a2, emd_value(sqdist3(o1.x - qx, o1.y - qy, o1.z - qz), o1.w));
           if (hint) top2_insert(a1, a2, emd_value(sqdist3(oh.x - qx, oh.y - qy, oh.z - qz), oh.w));
@@ -508,7 +419,7 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
               float4 o[kRowVisitLoads];
 #pragma unroll
               for (int r4 = 0; r4 < kRowVisitLoads; ++r4)
-                o[r4] = in[r4] ? ld_obj(s[r4] + 16 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
+                o[r4] = in[r4] ? sa.ld_obj(s[r4] + 16 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
               for (int r4 = 0; r4 < kRowVisitLoads; ++r4) consider(in[r4], o[r4], s[r4] + 16 * c);
             }
@@ -542,7 +453,7 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
             float4 o[4];
 #pragma unroll
             for (int r4 = 0; r4 < 4; ++r4)
-              o[r4] = linear ? ld_obj(base + r4 * 16 + l16) : make_float4(0.f, 0.f, 0.f, 0.f);
+              o[r4] = linear ? sa.ld_obj(base + r4 * 16 + l16) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
             for (int r4 = 0; r4 < 4; ++r4) consider(linear, o[r4], base + r4 * 16 + l16);
           }
@@ -585,7 +496,7 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
         }
         if (act && l16 == 0) {
           const float inc = lb1 - lb2 + eps;
-          st_person_hi(j, lbk, lbk, lb2k, inc);
+          sa.st_person_hi(j, lbk, lbk, lb2k, inc);
           if (u < kBidCache) {
             s_bj[u] = j;
             s_bo[u] = lbk;
@@ -616,10 +527,7 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
       const int j = rb.x;
       const float qx = ra.x, qy = ra.y, qz = ra.z;
       const int p1 = rb.y, p2 = rb.z;
-#ifdef MVP_EMD_PROFILE
-      const long long tb0 = __builtin_readcyclecounter();
-      int prof_cells = 0;
-#endif
+      EMD_PROF(EmdBidProbe bp;)
       const int hc = __float_as_int(ra.w);   // home chunk (emd_index.h)
       BidState st;
       st.b1 = -1e9f;
@@ -628,42 +536,11 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
       st.b2k = -1;
       unsigned short *wl = w_list[wave];
       int nsub = 0;          // leaves tested (statistics)
-#ifdef MVP_EMD_PROFILE
-      long long tb1 = tb0;
-      float prof_tm_seed = 0.f;
-      long long t_visit = 0;
-      int n_visit = 0, prof_fold = 0, prof_more = 0;
-#endif
 #define EMD_SEARCH_FOLD(m_, v_, slot_, price_) emd_fold(st, m_, v_, slot_, n, tpu, sc.perm)
 #include "emd_search_wave.inc"
 #undef EMD_SEARCH_FOLD
       (void)nsub;
-#ifdef MVP_EMD_PROFILE
-      if (lane == 0 && it >= 100) {
-        const long long d = __builtin_readcyclecounter() - tb0;
-        int bkt = 0;
-        while (bkt < 7 && d >= (2000ll << bkt)) ++bkt;
-        atomicAdd(&s_hist[bkt], 1ull);
-        atomicAdd(&s_hist[8], (unsigned long long)nsub);
-        atomicAdd(&s_hist[9], (unsigned long long)prof_cells);
-        atomicAdd(&s_hist[10], 1ull);
-        if (linear) atomicAdd(&s_hist[11], 1ull);
-        atomicAdd(&s_hist[12], (unsigned long long)d);
-        atomicAdd(&s_hist2[0], (unsigned long long)(tb1 - tb0));
-        atomicAdd(&s_hist2[1], (unsigned long long)t_visit);
-        atomicAdd(&s_hist2[2], (unsigned long long)n_visit);
-        atomicAdd(&s_hist2[3], (unsigned long long)prof_fold);
-        unsigned long long *sl = s_slow[d >= 10000 ? 1 : 0];
-        atomicAdd(&sl[0], 1ull);
-        atomicAdd(&sl[1], (unsigned long long)nsub);
-        atomicAdd(&sl[2], (unsigned long long)prof_cells);
-        atomicAdd(&sl[3], (unsigned long long)n_visit);
-        atomicAdd(&sl[4], (unsigned long long)prof_more);
-        atomicAdd(&sl[5], (unsigned long long)prof_fold);
-        atomicAdd(&sl[6], (unsigned long long)(tb1 - tb0));
-        atomicAdd(&sl[7], (unsigned long long)t_visit);
-      }
-#endif
+      EMD_PROF(if (lane == 0 && it >= 100) bp.done(pl, nsub, linear);)
       if (st.bk < 0) {  // cannot happen (>= 2 objects always survive); never index with -1
         if (lane == 0) s_err = 1;
         st.bk = 0;
@@ -671,7 +548,7 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
       }
       if (lane == 0) {
         const float inc = st.b1 - st.b2 + eps;
-        st_person_hi(j, st.bk, st.bk, st.b2k, inc);
+        sa.st_person_hi(j, st.bk, st.bk, st.b2k, inc);
         if (u < kBidCache) {
           s_bj[u] = j;
           s_bo[u] = st.bk;
@@ -699,10 +576,8 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
     int *my_alarm = &s_alarm[it & 1];
     if (alarm) *my_alarm = 1;
     if (t == 0) s_cnt[cur ^ 1] = 0;
-#ifdef MVP_EMD_PROFILE
-    const long long tp1 = __builtin_readcyclecounter();
-    if (lane == 0) s_wbusy[wave] = (int)(tp1 - tp0);
-#endif
+    EMD_PROF(const long long tp1 = __builtin_readcyclecounter();
+             if (lane == 0) pl.s_wbusy[wave] = (int)(tp1 - tp0);)
     // ---------------- all bids of the round are placed
     bool any_alarm;
     if (clustered) {
@@ -725,9 +600,7 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
     // bidder inside the band of the object's maximal increment raises the
     // key's bidder field; the increment field stays.
     if (__builtin_expect(any_alarm, 0)) {
-#ifdef MVP_EMD_PROFILE
-      n_alarm += 1;
-#endif
+      EMD_PROF(pr.n_alarm += 1;)
       for (int u = t; u < U; u += kEmdThreads) {
         int j, o;
         float bi;
@@ -735,10 +608,10 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
           j = s_bj[u]; o = s_bo[u]; bi = s_binc[u];
         } else {
           j = L[u];
-          const float4 g = ld_person(j, 1);
+          const float4 g = sa.ld_person(j, 1);
           o = __float_as_int(g.x); bi = g.w;
         }
-        const u64 key = ld_key(o);
+        const u64 key = sa.ld_key(o);
         if (emd_in_band(bi, emd_ord2f((unsigned)(key >> 32))))
           atomicMax(reinterpret_cast<u64 *>(&sc.ostate[o]), (key & 0xFFFFFFFF00000000ull) | (u64)((unsigned)j + 1u));
       }
@@ -755,9 +628,7 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
       s_alarm[(it + 1) & 1] = 0;  // next round's flag; its writers are a barrier away
       s_next = kEmdWaves;         // list positions 0..15 belong to the waves, the rest are drawn
     }
-#ifdef MVP_EMD_PROFILE
-    const long long tp2 = __builtin_readcyclecounter();
-#endif
+    EMD_PROF(const long long tp2 = __builtin_readcyclecounter();)
 
     // ---------------- Assign (emd_cuda.cu:196-215)
     const int nxt = cur ^ 1;
@@ -776,41 +647,35 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
         j = s_bj[u]; o = s_bo[u]; bi = s_binc[u]; b2k = s_b2k[u];
       } else {
         j = L[u];
-        const float4 g = ld_person(j, 1);
+        const float4 g = sa.ld_person(j, 1);
         o = __float_as_int(g.x); b2k = __float_as_int(g.z); bi = g.w;
       }
-#ifdef MVP_EMD_PROFILE
-      const long long ta0 = __builtin_readcyclecounter();
-#endif
-      const int4 os = ld_ostate(o);
-      const float4 oo = ld_obj(o);  // independent of `os`: same round trip
-#ifdef MVP_EMD_PROFILE
-      if (t == 0 && it >= 100) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        prof_a1 += __builtin_readcyclecounter() - ta0;
-        prof_an += 1;
-      }
-#endif
+      EMD_PROF(const long long ta0 = __builtin_readcyclecounter();)
+      const int4 os = sa.ld_ostate(o);
+      const float4 oo = sa.ld_obj(o);  // independent of `os`: same round trip
+      EMD_PROF(if (t == 0 && it >= 100) {
+                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                 pr.prof_a1 += __builtin_readcyclecounter() - ta0;
+                 pr.prof_an += 1;
+               })
       if (last || (unsigned)os.x == (unsigned)j + 1u) {  // a loser may read after the winner reset the key to 0
         const int prev = os.z;
         if (!last && prev != -1) {
           // the evicted owner bids again next round, in this workgroup's list
-          st_i32(&ass[prev], -1);
+          sa.st_i32(&ass[prev], -1);
           const int pos = atomicAdd(&s_cnt[nxt], 1);
           if (__builtin_expect(pos >= kRecCap, 0)) Lnext[pos] = prev;   // entries below kRecCap live in LDS only
           if (__builtin_expect(pos < kRecCap, 1)) {
-            const float4 pa = ld_person(prev, 0);
-            const float4 pb = ld_person(prev, 1);
+            const float4 pa = sa.ld_person(prev, 0);
+            const float4 pb = sa.ld_person(prev, 1);
             s_rq[nxt][pos] = pa;
             s_ri[nxt][pos] = make_int4(prev, __float_as_int(pb.y), __float_as_int(pb.z), 0);
           }
         }
-#ifdef MVP_EMD_PROFILE
-        if (t == 0 && it >= 100) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); prof_a2 += __builtin_readcyclecounter() - ta0; }
-#endif
-        st_ostate(o, j);
-        st_i32(&ass[j], o);
-        st_f32(&sc.obj[o].w, oo.w + bi);
+        EMD_PROF(if (t == 0 && it >= 100) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); pr.prof_a2 += __builtin_readcyclecounter() - ta0; })
+        sa.st_ostate(o, j);
+        sa.st_i32(&ass[j], o);
+        sa.st_f32(&sc.obj[o].w, oo.w + bi);
         // The leaf's price lower bound only needs a refresh when the object
         // that just got dearer was (one of) the cheapest of its leaf; then the
         // members are re-scanned (prices read while other winners raise them
@@ -823,14 +688,12 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
           // (the first 16 members in ONE round trip: all of them up to 16384 points)
           float pv[16];
 #pragma unroll
-          for (int k = 0; k < 16; ++k) pv[k] = e0 + k != o ? ld_price(e0 + k) : __builtin_inff();
+          for (int k = 0; k < 16; ++k) pv[k] = e0 + k != o ? sa.ld_price(e0 + k) : __builtin_inff();
 #pragma unroll
           for (int k = 0; k < 16; ++k) pm = __builtin_fminf(pm, pv[k]);
-          for (int s = e0 + 16; s < e1; ++s) pm = __builtin_fminf(pm, s == o ? pm : ld_price(s));
+          for (int s = e0 + 16; s < e1; ++s) pm = __builtin_fminf(pm, s == o ? pm : sa.ld_price(s));
           l_lo[c].w = pm;
-#ifdef MVP_EMD_PROFILE
-          if (it >= 100) atomicAdd(&s_hist2[0], 1ull << 40);  // refresh count in the high bits
-#endif
+          EMD_PROF(if (it >= 100) atomicAdd(&pl.s_hist2[0], 1ull << 40);)   // refresh count in the high bits
           if (clustered) {
             const int q = atomicAdd(&s_nchg, 1);
             if (q < kChgCap) {
@@ -849,36 +712,28 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
           if (u < kRecCap)
             pa = s_rq[cur][u];
           else
-            pa = ld_person(j, 0);
+            pa = sa.ld_person(j, 0);
           s_rq[nxt][pos] = pa;
           s_ri[nxt][pos] = make_int4(j, o, b2k, 0);
         }
       }
-#ifdef MVP_EMD_PROFILE
-      if (t == 0 && it >= 100) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); prof_a3 += __builtin_readcyclecounter() - ta0; }
-#endif
+      EMD_PROF(if (t == 0 && it >= 100) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); pr.prof_a3 += __builtin_readcyclecounter() - ta0; })
     }
     // the nodes' price bounds follow their leaves' (LDS only; a bound that lags a round is still a bound)
     if (t >= kEmdThreads - kMaxNodes) emd_node_price(l_lo, n_lo, t - (kEmdThreads - kMaxNodes), nleaf);
-#ifdef MVP_EMD_PROFILE
-    const long long tp3 = __builtin_readcyclecounter();
-    if (t == 0 && it >= 100) prof_a4 += tp3 - tp2;
-#endif
+    EMD_PROF(const long long tp3 = __builtin_readcyclecounter();
+             if (t == 0 && it >= 100) pr.prof_a4 += tp3 - tp2;)
     // ---------------- end of round: next list sizes + refreshed price bounds
     if (clustered) {
-#ifdef MVP_EMD_PROFILE
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const long long tpd = __builtin_readcyclecounter();
-#endif
+      EMD_PROF(asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+               const long long tpd = __builtin_readcyclecounter();)
       if (!emd_cluster_gather<W>(slots, wg, ++epoch, &s_cnt[nxt], &s_nchg, s_gout, &s_abort, same_xcd)) {
         aborted = true;
         break;
       }
-#ifdef MVP_EMD_PROFILE
-      const long long tpg2 = __builtin_readcyclecounter();
-      prof_drain += tpd - tp3;
-      prof_gather += tpg2 - tpd;
-#endif
+      EMD_PROF(const long long tpg2 = __builtin_readcyclecounter();
+               pr.prof_drain += tpd - tp3;
+               pr.prof_gather += tpg2 - tpd;)
       Utot = 0;
       bool overflow = false;
       int cntw[W], chgw[W];  // (the same for every lane: kept in scalar registers, the arithmetic on them is SALU work)
@@ -909,9 +764,7 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
               resume->first_it = it + 1;
               resume->next_it = it + 1;
               stats[0] = n_rounds;
-#ifdef MVP_EMD_CLOUDTIME
-              sc.chg[(size_t)kMaxCluster * kChgCap - 64 + 62] = ((u64)W << 48) | ((u64)Utot << 32) | (u64)(unsigned)(wall_clock64() - ct_a0);
-#endif
+              EMD_CTIME(sc.chg[(size_t)kMaxCluster * kChgCap - 64 + 62] = emd_ctime_word(W, Utot, wall_clock64() - ct_a0);)
             }
           }
           return;
@@ -920,7 +773,7 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
       if (__builtin_expect(Utot > 0 && Utot <= kSoloMax && it + 1 < iters, 0)) {
         // ---- hand everything to member 0 (lists of <= kSoloMax persons live
         // in LDS only: publish the person ids; their records are in memory)
-        if (wg != 0 && t < cntw[wg]) st_i32(my_ulist + t, s_ri[nxt][t].x);
+        if (wg != 0 && t < cntw[wg]) sa.st_i32(my_ulist + t, s_ri[nxt][t].x);
         if (!emd_cluster_gather<W>(slots, wg, ++epoch, &s_nchg, &s_nchg, s_gout, &s_abort, same_xcd)) {
           aborted = true;
           break;
@@ -935,8 +788,8 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
           if (idx >= 0 && idx < cntw[w]) {
             const int jj = __hip_atomic_load(sc.ulist + (size_t)w * 2 * n + idx, __ATOMIC_RELAXED,
                                              __HIP_MEMORY_SCOPE_AGENT);
-            const float4 pa = ld_person(jj, 0);
-            const float4 pb = ld_person(jj, 1);
+            const float4 pa = sa.ld_person(jj, 0);
+            const float4 pb = sa.ld_person(jj, 1);
             const int pos = atomicAdd(&s_cnt[nxt], 1);
             s_rq[nxt][pos] = pa;
             s_ri[nxt][pos] = make_int4(jj, __float_as_int(pb.y), __float_as_int(pb.z), 0);
@@ -977,7 +830,7 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
           int *dead = my_ulist + (size_t)cur * n;   // this round's list: no longer read
           for (int i = t; i < my_exc; i += kEmdThreads) {
             const int pos = my_cnt - my_exc + i;
-            st_i32(dead + i, pos < kRecCap ? s_ri[nxt][pos].x : Lnext[pos]);
+            sa.st_i32(dead + i, pos < kRecCap ? s_ri[nxt][pos].x : Lnext[pos]);
           }
           if (!emd_cluster_gather<W>(slots, wg, ++epoch, &s_nchg, &s_nchg, s_gout, &s_abort, same_xcd)) {
             aborted = true;
@@ -994,8 +847,8 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
             }
             const int pos = my_cnt + i;
             if (pos < kRecCap) {
-              const float4 pa = ld_person(jj, 0);
-              const float4 pb = ld_person(jj, 1);
+              const float4 pa = sa.ld_person(jj, 0);
+              const float4 pb = sa.ld_person(jj, 1);
               s_rq[nxt][pos] = pa;
               s_ri[nxt][pos] = make_int4(jj, __float_as_int(pb.y), __float_as_int(pb.z), 0);
             } else {
@@ -1004,15 +857,11 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
           }
           if (t == 0) s_cnt[nxt] = my_cnt - my_exc + my_dfc;
           __syncthreads();
-#ifdef MVP_EMD_PROFILE
-          n_rebal += 1;
-#endif
+          EMD_PROF(pr.n_rebal += 1;)
         }
       }
-#ifdef MVP_EMD_PROFILE
-      const long long tpb = __builtin_readcyclecounter();
-      prof_pg1 += tpb - tpg2;
-#endif
+      EMD_PROF(const long long tpb = __builtin_readcyclecounter();
+               pr.prof_pg1 += tpb - tpg2;)
       if (!clustered) {
         // (just collapsed: nothing to fetch)
       } else if (__builtin_expect(overflow, 0)) {
@@ -1020,7 +869,7 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
         // every bound from the prices themselves (stable between barriers)
         for (int c = t; c < nleaf; c += kEmdThreads) {
           float pm = __builtin_inff();
-          for (int s = c << lshift; s < ((c + 1) << lshift); ++s) pm = __builtin_fminf(pm, ld_obj(s).w);
+          for (int s = c << lshift; s < ((c + 1) << lshift); ++s) pm = __builtin_fminf(pm, sa.ld_obj(s).w);
           if (pm >= l_lo[c].w) l_lo[c].w = pm;
         }
       } else {
@@ -1081,28 +930,20 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
         return;
       }
     }
-#ifdef MVP_EMD_PROFILE
-    const long long tp4 = __builtin_readcyclecounter();
-    cyc_bid += tp1 - tp0; cyc_sync1 += tp2 - tp1; cyc_assign += tp3 - tp2; cyc_sync2 += tp4 - tp3;
-    if (t == 0 && it >= 100 && U <= kRowModeMin) {
-      int mx = 0, sm = 0;
-      for (int w = 0; w < kEmdWaves; ++w) { mx = max(mx, s_wbusy[w]); sm += s_wbusy[w]; }
-      s_hist[13] += mx; s_hist[14] += sm / kEmdWaves; s_hist[15] += 1; prof_u += U;
-    }
-#endif
+    EMD_PROF(const long long tp4 = __builtin_readcyclecounter();
+             pr.cyc_bid += tp1 - tp0; pr.cyc_sync1 += tp2 - tp1; pr.cyc_assign += tp3 - tp2; pr.cyc_sync2 += tp4 - tp3;
+             if (t == 0 && it >= 100 && U <= kRowModeMin) pr.round_end(pl, U);)
     cur ^= 1;
   }
 
-#ifdef MVP_EMD_PROFILE
-  if (clustered && !aborted) {  // cost of the bare all-gather
-    const long long tg0 = __builtin_readcyclecounter();
-    for (int g = 0; g < 256; ++g)
-      if (!emd_cluster_gather<W>(slots, wg, ++epoch, &s_nchg, &s_nchg, s_gout, &s_abort, same_xcd)) break;
-    if (t == 0 && cloud < 2 && wg == 0)
-      printf("cloud %d: bare cluster all-gather %lld cycles each (W = %d, same_xcd %d)\n", cloud,
-             (__builtin_readcyclecounter() - tg0) / 256, W, (int)same_xcd);
-  }
-#endif
+  EMD_PROF(if (clustered && !aborted) {   // cost of the bare all-gather
+             const long long tg0 = __builtin_readcyclecounter();
+             for (int g = 0; g < 256; ++g)
+               if (!emd_cluster_gather<W>(slots, wg, ++epoch, &s_nchg, &s_nchg, s_gout, &s_abort, same_xcd)) break;
+             if (t == 0 && cloud < 2 && wg == 0)
+               printf("cloud %d: bare cluster all-gather %lld cycles each (W = %d, same_xcd %d)\n", cloud,
+                      (__builtin_readcyclecounter() - tg0) / 256, W, (int)same_xcd);
+           })
   if (aborted) {
     // A cluster wait ran into its bound (the members were not co-resident for
     // tens of seconds).  Fail loudly: NaN distances, -1 assignments.
@@ -1117,34 +958,7 @@ __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
     if (wg == 0) stats[0] = s_err ? -1 : n_rounds;
     if (s_err) stats[0] = -1;
     atomicAdd(reinterpret_cast<unsigned long long *>(&stats[1]), (unsigned long long)n_bids);
-#ifdef MVP_EMD_PROFILE
-    if (cloud < 2)
-      printf("cloud %d wg %d per wave-mode bid: seed %llu cycles, visits %llu cycles in %.2f steps folding %.1f candidates, rest (enumeration, finish) %llu\n", cloud, wg,
-             s_hist2[0] / (s_hist[10] + 1), s_hist2[1] / (s_hist[10] + 1), (double)s_hist2[2] / (double)(s_hist[10] + 1), (double)s_hist2[3] / (double)(s_hist[10] + 1),
-             (s_hist[12] - s_hist2[0] - s_hist2[1]) / (s_hist[10] + 1));
-    if (cloud < 2)
-      printf("cloud %d wg %d price-bound refreshes after round 100: %llu\n", cloud, wg, s_hist2[0] >> 40);
-    if (cloud == 0 && wg == 0)
-      for (int k = 0; k < 2; ++k) {
-        const double c = (double)s_slow[k][0] + 1e-9;
-        printf("cloud 0 wg 0 searches %s 10k cycles: %llu | mean sub-box %.0f cells, visited %.1f, visit steps %.2f, extra member iterations %.2f, folds %.1f, seed %.0f cycles, visits %.0f cycles\n",
-               k ? ">=" : "<", s_slow[k][0], s_slow[k][1] / c, s_slow[k][2] / c, s_slow[k][3] / c, s_slow[k][4] / c, s_slow[k][5] / c, s_slow[k][6] / c, s_slow[k][7] / c);
-      }
-    if (cloud < 2)
-      printf("cloud %d wg %d Assign (thread 0, %lld samples): loads done at %lld cycles, eviction handled at %lld (sum over winning rounds / all), body done at %lld, phase %lld\n", cloud, wg, prof_an, prof_a1 / (prof_an + 1), prof_a2 / (prof_an + 1), prof_a3 / (prof_an + 1), prof_a4 / (prof_an + 1));
-    if (cloud < 2)
-      printf("cloud %d wg %d tail rounds %llu: bidders/round %.1f, busiest wave %llu cycles/round, mean wave %llu\n", cloud, wg, s_hist[15],
-             (double)prof_u / (double)(s_hist[15] + 1), s_hist[13] / (s_hist[15] + 1), s_hist[14] / (s_hist[15] + 1));
-    if (cloud < 2)
-      printf("cloud %d wg %d wave-mode bids after round 100: %llu, mean cycles %llu, mean sub-box cells %llu, mean cells visited %llu, linear %llu | <2k %llu <4k %llu <8k %llu <16k %llu <32k %llu <64k %llu <128k %llu more %llu\n",
-             cloud, wg, s_hist[10], s_hist[12] / (s_hist[10] + 1), s_hist[8] / (s_hist[10] + 1), s_hist[9] / (s_hist[10] + 1), s_hist[11],
-             s_hist[0], s_hist[1], s_hist[2], s_hist[3], s_hist[4], s_hist[5], s_hist[6], s_hist[7]);
-    if (cloud < 2)
-      printf("cloud %d wg %d: rounds %lld bids %lld alarms %lld rebalances %lld | cycles bid %lld sync1 %lld assign %lld sync2 %lld \n",
-             cloud, wg, n_rounds, n_bids, n_alarm, n_rebal, cyc_bid, cyc_sync1, cyc_assign, cyc_sync2);
-    if (cloud < 2)
-      printf("cloud %d wg %d: sync2 = store drain %lld + closing gather %lld + list bookkeeping %lld + bound fetch (rest)\n", cloud, wg, prof_drain, prof_gather, prof_pg1);
-#endif
+    EMD_PROF(emd_probe_report(false, pl, pr, cloud, wg, n_rounds, n_bids);)
   }
   // ---------------- CalcDist (emd_cuda.cu:217-226); slots -> object indices
   __syncthreads();
@@ -1197,10 +1011,25 @@ struct EmdKnobs {
   unsigned long long plan_widths; // widths of an XCD's 8 cloud slots, heaviest first, 4 bits each
   int res_cap;                    // split == 3: unassigned persons at which a cloud of <= 4096 points moves into LDS (emd_resident.hip)
 };
+// The compiled-in defaults: of the process-wide knobs and of every mvp_emd_forward_plan call.
+static EmdKnobs emd_default_knobs() {
+  return EmdKnobs{kMaxCluster, 1, 5, 300, 4096, 0ull, 16};   // plan_widths 0: from the loads (MVP_EMD_PLAN_WIDTHS=8,5,4,4,3,3,3,2 fixes them)
+}
+// The four public fields (mvp_emd_configure's arguments, MvpEmdPlan's members) into `k`: negative = keep.  All four are
+// checked before anything is written, so a rejected call changes nothing.
+static int emd_apply_knobs(EmdKnobs &k, int cluster, int same_xcd, int split, int resident_cap) {
+  if (resident_cap == 0 || resident_cap > kResList) return MVP_EBADARG;
+  if (cluster > 0 && cluster != 1 && cluster != 2 && cluster != 4 && cluster != 8) return MVP_EBADARG;
+  if (cluster >= 0) k.cluster = cluster == 0 ? kMaxCluster : cluster;
+  if (same_xcd >= 0) k.same_xcd = same_xcd != 0;
+  if (split >= 0) k.split = split > 5 ? 5 : split;
+  if (resident_cap > 0) k.res_cap = resident_cap;
+  return MVP_OK;
+}
 static std::mutex g_knob_mutex;
 static EmdKnobs &emd_knobs_locked() {   // (callers hold g_knob_mutex)
   static EmdKnobs k = [] {
-    EmdKnobs v{kMaxCluster, 1, 5, 300, 4096, 0ull, 16};   // (mvp_emd_forward_plan builds the same defaults) widths from the loads (MVP_EMD_PLAN_WIDTHS=8,5,4,4,3,3,3,2 fixes them)
+    EmdKnobs v = emd_default_knobs();
 #ifdef MVP_TEST_HOOKS
     if (const char *e = getenv("MVP_EMD_CLUSTER")) v.cluster = atoi(e);
     if (const char *e = getenv("MVP_EMD_SAME_XCD")) v.same_xcd = atoi(e) != 0;
@@ -1269,16 +1098,7 @@ extern "C" long long mvp_emd_scratch_bytes(int b, int n) {
 
 extern "C" int mvp_emd_configure(int cluster, int same_xcd, int split, int resident_cap) {
   std::lock_guard<std::mutex> g(g_knob_mutex);
-  EmdKnobs &k = emd_knobs_locked();
-  if (resident_cap == 0 || resident_cap > kResList) return MVP_EBADARG;
-  if (resident_cap > 0) k.res_cap = resident_cap;
-  if (cluster >= 0) {
-    if (cluster != 0 && cluster != 1 && cluster != 2 && cluster != 4 && cluster != 8) return MVP_EBADARG;
-    k.cluster = cluster == 0 ? kMaxCluster : cluster;
-  }
-  if (same_xcd >= 0) k.same_xcd = same_xcd != 0;
-  if (split >= 0) k.split = split > 5 ? 5 : split;
-  return MVP_OK;
+  return emd_apply_knobs(emd_knobs_locked(), cluster, same_xcd, split, resident_cap);
 }
 
 static int emd_forward_with(const EmdKnobs &knobs, int b, int n, const float *xyz1,
@@ -1335,17 +1155,8 @@ extern "C" int mvp_emd_forward_plan(int b, int n, const float *xyz1,
                                     const float *xyz2, float *dist, int *assignment,
                                     float eps, int iters, void *scratch,
                                     long long scratch_bytes, const MvpEmdPlan *plan, void *stream) {
-  EmdKnobs k{kMaxCluster, 1, 5, 300, 4096, 0ull, 16};
-  if (plan) {
-    if (plan->cluster >= 0) {
-      if (plan->cluster != 0 && plan->cluster != 1 && plan->cluster != 2 && plan->cluster != 4 && plan->cluster != 8) return MVP_EBADARG;
-      k.cluster = plan->cluster == 0 ? kMaxCluster : plan->cluster;
-    }
-    if (plan->same_xcd >= 0) k.same_xcd = plan->same_xcd != 0;
-    if (plan->split >= 0) k.split = plan->split > 5 ? 5 : plan->split;
-    if (plan->resident_cap == 0 || plan->resident_cap > kResList) return MVP_EBADARG;
-    if (plan->resident_cap > 0) k.res_cap = plan->resident_cap;
-  }
+  EmdKnobs k = emd_default_knobs();
+  if (plan && emd_apply_knobs(k, plan->cluster, plan->same_xcd, plan->split, plan->resident_cap) != MVP_OK) return MVP_EBADARG;
   return emd_forward_with(k, b, n, xyz1, xyz2, dist, assignment, eps, iters, scratch, scratch_bytes, stream);
 }
 

@@ -150,6 +150,100 @@ __device__ __forceinline__ EmdScratch emd_carve(char *base, int n) {
   return s;
 }
 
+// Accessors of the shared auction state of one cloud, for a cluster of W workgroups (emd_auction_kernel<W>,
+// emd_lean_body<W> and the fragments included into them).  W == 1: plain.  W > 1: loads
+// bypass this CU's L1 (sc1), stores are written through (sc1), so data is
+// visible to the other workgroups once the store is acknowledged.
+// The members are references to the kernel's own locals, like a lambda's captures: `rs` = the buffer resource of the
+// cloud's scratch area, `same_xcd` = the kernel's flag, which it sets AFTER this object exists (the cluster's first gather).
+typedef decltype(__builtin_amdgcn_make_buffer_rsrc((void *)nullptr, (short)0, 0, 0)) EmdRsrc;
+template <int W>
+struct EmdShared {
+  const EmdRsrc &rs;
+  const EmdScratch &sc;
+  const int &n;
+  // Stores of shared words.  When every member of the cluster was observed on
+  // the same XCD (same_xcd) they share one L2, the coherence point of
+  // that XCD's CUs: a plain store (L1 is write-through) is visible to the
+  // others' L1-bypassing loads as soon as it is acknowledged, and the line
+  // stays in L2 instead of being written through to memory and dropped.
+  const bool &same_xcd;
+
+  __device__ __forceinline__ float4 ld_obj(int s) const {
+    if constexpr (W == 1) {
+      return sc.obj[s];
+    } else {
+      const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rs, (unsigned)s * 16u, 0, 16);
+      return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+    }
+  }
+  __device__ __forceinline__ float ld_price(int s) const {  // obj[s].w alone
+    if constexpr (W == 1) return sc.obj[s].w;
+    else return __uint_as_float((unsigned)__builtin_amdgcn_raw_buffer_load_b32(rs, (unsigned)s * 16u + 12u, 0, 16));
+  }
+  __device__ __forceinline__ int4 ld_ostate(int s) const {
+    if constexpr (W == 1) {
+      return sc.ostate[s];
+    } else {
+      const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rs, ((unsigned)n + (unsigned)s) * 16u, 0, 16);
+      return make_int4((int)v.x, (int)v.y, (int)v.z, (int)v.w);
+    }
+  }
+  __device__ __forceinline__ float4 ld_person(int j, int half) const {  // half 0 = lo, 1 = hi
+    if constexpr (W == 1) {
+      return sc.person[2 * j + half];
+    } else {
+      const v4u v =
+          __builtin_amdgcn_raw_buffer_load_b128(rs, (2u * (unsigned)n + 2u * (unsigned)j + (unsigned)half) * 16u, 0, 16);
+      return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+    }
+  }
+  __device__ __forceinline__ void st_person_hi(int j, int bid, int p1, int p2, float inc) const {
+    if constexpr (W == 1) {
+      sc.person[2 * j + 1] = make_float4(__int_as_float(bid), __int_as_float(p1), __int_as_float(p2), inc);
+    } else {
+      v4u v;
+      v.x = (unsigned)bid; v.y = (unsigned)p1; v.z = (unsigned)p2; v.w = __float_as_uint(inc);
+      if (same_xcd) __builtin_amdgcn_raw_buffer_store_b128(v, rs, (2u * (unsigned)n + 2u * (unsigned)j + 1u) * 16u, 0, 0);
+      else __builtin_amdgcn_raw_buffer_store_b128(v, rs, (2u * (unsigned)n + 2u * (unsigned)j + 1u) * 16u, 0, 16);
+    }
+  }
+  __device__ __forceinline__ void st_ostate(int s, int owner) const {  // key = 0 (no bid), new owner
+    if constexpr (W == 1) {
+      sc.ostate[s] = make_int4(0, 0, owner, 0);
+    } else {
+      v4u v;
+      v.x = 0u; v.y = 0u; v.z = (unsigned)owner; v.w = 0u;
+      if (same_xcd) __builtin_amdgcn_raw_buffer_store_b128(v, rs, ((unsigned)n + (unsigned)s) * 16u, 0, 0);
+      else __builtin_amdgcn_raw_buffer_store_b128(v, rs, ((unsigned)n + (unsigned)s) * 16u, 0, 16);
+    }
+  }
+  __device__ __forceinline__ void st_i32(int *p, int v) const {
+    if constexpr (W == 1) *p = v;
+    else if (same_xcd) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    else __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __device__ __forceinline__ void st_f32(float *p, float v) const {
+    if constexpr (W == 1) *p = v;
+    else if (same_xcd) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    else __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __device__ __forceinline__ u64 ld_key(int s) const {
+    u64 *p = reinterpret_cast<u64 *>(&sc.ostate[s]);
+    if constexpr (W == 1) return *p;
+    else return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+};
+
+// A cluster wait ran into its bound (the members were not co-resident for
+// tens of seconds).  Fail loudly: NaN distances, -1 assignments.
+__device__ __forceinline__ void emd_abort_fill(float *dist, int *ass, int n) {
+  for (int j = threadIdx.x; j < n; j += kEmdThreads) {
+    dist[j] = __builtin_nanf("");
+    ass[j] = -1;
+  }
+}
+
 // Order-preserving map float -> unsigned (and back); never 0 for a non-NaN.
 __device__ __forceinline__ unsigned emd_f2ord(float f) {
   const unsigned u = __float_as_uint(f);

@@ -16,16 +16,21 @@
 //   emd_lean_kernel<W>      every cloud on the cluster width the first kernel ran with
 //   emd_lean_tiers_kernel   from round 300 on: the workgroups dealt out again, 8 .. 2 per cloud by the
 //                           clouds' load (a launch lasts as long as its slowest cloud; DESIGN.md 5.2, notebook 5e)
-// The round loop of emd_lean_body is kept in four fragments included into it (round 5; one file had grown to 1766 lines):
+// The round loop of emd_lean_body is kept in fragments included into it (round 5; one file had grown to 1766 lines):
 //   emd_lean_bid.inc             Bid: one wave per bidder (both round shapes)
 //   emd_lean_round_plain.inc     plain rounds: bid atomics, all-gather, GetMax, Assign
 //   emd_lean_round_gathered.inc  gathered-bid rounds: bid records, one cluster-wide wait, every member settles every bid
 //   emd_lean_round_end.inc       list sizes, hand-over / stop checks, price bounds, entry into the gathered rounds
+//   emd_lean_round_few.inc       a collapsed cluster's rounds of at most 16 bidders (the `few` lambda)
+// The accessors of the shared auction state (sa.ld_obj, sa.st_ostate, ...) are EmdShared<W> of emd_common.h, the same as
+// emd_auction_kernel's; the probes of the instrumented builds (EMD_PROF, EMD_CTIME, GMT) are emd_probe.h's and expand to
+// nothing in the release build.
 #include <cstdlib>
 #include <type_traits>
 
 #include "emd_common.h"
 #include "emd_index.h"
+#include "emd_probe.h"
 #include "emd_resident.h"
 
 namespace mvp {
@@ -69,13 +74,7 @@ struct LeanShared {
   // parity, bidders of the round by round % 3
   alignas(16) int f_cnt[2][256];
   int f_act[3];
-#ifdef MVP_EMD_PROFILE
-  int s_wbusy[kEmdWaves];
-  unsigned long long s_hist2[4];
-  float s_loose[2][3];
-  unsigned long long s_slow[2][8];
-  unsigned long long s_hist[16];
-#endif
+  EMD_PROF(EmdProbeLds probe;)
 };
 
 // The remaining rounds of one cloud on a cluster of WB workgroups, of which this is member `wg`.
@@ -112,80 +111,11 @@ __device__ __forceinline__ int emd_lean_body(LeanShared &sh, const int cloud, co
   int *ass = assignment + (size_t)cloud * n;
   const EmdScratch sc = emd_carve(cbase, n);
 
-  // ---- accessors of the shared auction state.  W == 1: plain.  W > 1: loads
-  // bypass this CU's L1 (sc1), stores are written through (sc1), so data is
-  // visible to the other workgroups once the store is acknowledged.
+  // ---- accessors of the shared auction state (emd_common.h): sa.ld_obj(slot), sa.st_ostate(slot, owner), ...
+  // same_xcd is set below, after the cluster's first gather; the accessors read it through a reference.
   const auto rs = __builtin_amdgcn_make_buffer_rsrc(cbase, 0, (int)emd_scratch_per_cloud(n), 0x00020000);
-  auto ld_obj = [&](int s) -> float4 {
-    if constexpr (WB == 1) {
-      return sc.obj[s];
-    } else {
-      const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rs, (unsigned)s * 16u, 0, 16);
-      return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-    }
-  };
-  auto ld_price = [&](int s) -> float {  // obj[s].w alone
-    if constexpr (WB == 1) return sc.obj[s].w;
-    else return __uint_as_float((unsigned)__builtin_amdgcn_raw_buffer_load_b32(rs, (unsigned)s * 16u + 12u, 0, 16));
-  };
-  auto ld_ostate = [&](int s) -> int4 {
-    if constexpr (WB == 1) {
-      return sc.ostate[s];
-    } else {
-      const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rs, ((unsigned)n + (unsigned)s) * 16u, 0, 16);
-      return make_int4((int)v.x, (int)v.y, (int)v.z, (int)v.w);
-    }
-  };
-  auto ld_person = [&](int j, int half) -> float4 {  // half 0 = lo, 1 = hi
-    if constexpr (WB == 1) {
-      return sc.person[2 * j + half];
-    } else {
-      const v4u v =
-          __builtin_amdgcn_raw_buffer_load_b128(rs, (2u * (unsigned)n + 2u * (unsigned)j + (unsigned)half) * 16u, 0, 16);
-      return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-    }
-  };
-  // Stores of shared words.  When every member of the cluster was observed on
-  // the same XCD (same_xcd, below) they share one L2, the coherence point of
-  // that XCD's CUs: a plain store (L1 is write-through) is visible to the
-  // others' L1-bypassing loads as soon as it is acknowledged, and the line
-  // stays in L2 instead of being written through to memory and dropped.
   bool same_xcd = false;
-  auto st_person_hi = [&](int j, int bid, int p1, int p2, float inc) {
-    if constexpr (WB == 1) {
-      sc.person[2 * j + 1] = make_float4(__int_as_float(bid), __int_as_float(p1), __int_as_float(p2), inc);
-    } else {
-      v4u v;
-      v.x = (unsigned)bid; v.y = (unsigned)p1; v.z = (unsigned)p2; v.w = __float_as_uint(inc);
-      if (same_xcd) __builtin_amdgcn_raw_buffer_store_b128(v, rs, (2u * (unsigned)n + 2u * (unsigned)j + 1u) * 16u, 0, 0);
-      else __builtin_amdgcn_raw_buffer_store_b128(v, rs, (2u * (unsigned)n + 2u * (unsigned)j + 1u) * 16u, 0, 16);
-    }
-  };
-  auto st_ostate = [&](int s, int owner) {  // key = 0 (no bid), new owner
-    if constexpr (WB == 1) {
-      sc.ostate[s] = make_int4(0, 0, owner, 0);
-    } else {
-      v4u v;
-      v.x = 0u; v.y = 0u; v.z = (unsigned)owner; v.w = 0u;
-      if (same_xcd) __builtin_amdgcn_raw_buffer_store_b128(v, rs, ((unsigned)n + (unsigned)s) * 16u, 0, 0);
-      else __builtin_amdgcn_raw_buffer_store_b128(v, rs, ((unsigned)n + (unsigned)s) * 16u, 0, 16);
-    }
-  };
-  auto st_i32 = [&](int *p, int v) {
-    if constexpr (WB == 1) *p = v;
-    else if (same_xcd) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
-  auto st_f32 = [&](float *p, float v) {
-    if constexpr (WB == 1) *p = v;
-    else if (same_xcd) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
-  auto ld_key = [&](int s) -> u64 {
-    u64 *p = reinterpret_cast<u64 *>(&sc.ostate[s]);
-    if constexpr (WB == 1) return *p;
-    else return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
+  const EmdShared<WB> sa{rs, sc, n, same_xcd};
 
 
   auto &l_lo = sh.l_lo; auto &l_hi = sh.l_hi; auto &n_lo = sh.n_lo; auto &n_hi = sh.n_hi;
@@ -195,17 +125,7 @@ __device__ __forceinline__ int emd_lean_body(LeanShared &sh, const int cloud, co
   auto &s_err = sh.s_err; auto &s_abort = sh.s_abort; auto &s_nchg = sh.s_nchg; auto &s_xcc = sh.s_xcc;
   auto &s_alarm = sh.s_alarm;  // by round parity: set in Bid, read after the barrier, cleared a round later
   auto &s_gout = sh.s_gout;
-#ifdef MVP_EMD_PROFILE
-  auto &s_wbusy = sh.s_wbusy;
-  auto &s_hist2 = sh.s_hist2;
-  if (threadIdx.x < 4) s_hist2[threadIdx.x] = 0;
-  auto &s_loose = sh.s_loose;  // [slow][sum of (seed threshold - final threshold) in cell widths, sum of seed threshold, evicted (no bid last round) count]
-  if (threadIdx.x < 6) s_loose[threadIdx.x / 3][threadIdx.x % 3] = 0.f;
-  auto &s_slow = sh.s_slow;  // [d >= 10k cycles][count, nsub, cells, visit steps, extra member iterations, folds, seed cycles, visit cycles]
-  if (threadIdx.x < 16) s_slow[threadIdx.x >> 3][threadIdx.x & 7] = 0;
-  auto &s_hist = sh.s_hist;  // bids: [0..7] duration buckets, [8] sum nsub, [9] sum cells visited, [10] count, [11] linear scans, [12] sum cycles
-  if (threadIdx.x < 16) s_hist[threadIdx.x] = 0;
-#endif
+  EMD_PROF(EmdProbeLds &pl = sh.probe; pl.clear();)
   // this round's bids, by list position
   auto &s_bj = sh.s_bj; auto &s_bo = sh.s_bo; auto &s_b2k = sh.s_b2k;
   auto &s_binc = sh.s_binc;
@@ -280,10 +200,7 @@ __device__ __forceinline__ int emd_lean_body(LeanShared &sh, const int cloud, co
     for (int w = 1; w < WM; ++w) same_xcd &= w >= W || s_gout[2 * w] == s_gout[0];
     if (!ok) {
       if (wg == 0 && t == 0) stats[0] = -2;
-      for (int j = t; j < n; j += kEmdThreads) {
-        dist[j] = __builtin_nanf("");
-        ass[j] = -1;
-      }
+      emd_abort_fill(dist, ass, n);
       return 0;
     }
   } else {
@@ -306,14 +223,7 @@ __device__ __forceinline__ int emd_lean_body(LeanShared &sh, const int cloud, co
   const bool gm_ok = WB != 1 && n <= kGMaxN && (fast_ok & 2) != 0;   // (fast_ok: bit 0 = same-XCD stores, bit 1 = gathered-bid rounds)
   unsigned eg = (unsigned)resume->epoch_g;
   int goff = 0, gi = 0;
-#ifdef MVP_EMD_GMTIME
-  // phase clock of the gathered-bid rounds as wave 0 of member 0 sees them (cycles, summed over the rounds; tools/emd_gm_times.py)
-  long long gmt[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  long long gm_prev = 0;
-#define GMT(i) { const long long now_ = __builtin_readcyclecounter(); gmt[i] += now_ - gm_prev; gm_prev = now_; }
-#else
-#define GMT(i)
-#endif
+  EMD_GMTIME(long long gmt[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; long long gm_prev = 0;)   // phase clock (emd_probe.h: GMT)
   // The rounds of at most 16 bidders (emd_lean_round_few.inc) take a collapsed cluster's cloud when the leaves hold 16 slots
   // (n <= 16384 = the owner map's size) and this launch runs to the auction's end; a resident hand-over below 16 persons
   // -- a test knob -- keeps the plain rounds (they watch for it).  (A lambda, evaluated where it is needed: two more
@@ -322,18 +232,8 @@ __device__ __forceinline__ int emd_lean_body(LeanShared &sh, const int cloud, co
   constexpr int kLeanSoloMax = kFewMax > kSoloMax ? kFewMax : kSoloMax;   // persons at which the cluster collapses to member 0
   int stop_cnt = -1;   // >= 0: the loop ended before round it + 1 with this many entries in this member's next list
   bool stop_for_res = false;   // ... because at most u_stop persons are left (not because round it_stop is next)
-#ifdef MVP_EMD_PROFILE
-  long long prof_gap = 0, prof_prev4 = 0;
-  long long prof_pg1 = 0, prof_drain = 0, prof_gather = 0, cyc_bid = 0, cyc_sync1 = 0, cyc_assign = 0, cyc_sync2 = 0, n_alarm = 0, n_rebal = 0, prof_u = 0, prof_a1 = 0, prof_an = 0, prof_a2 = 0, prof_a3 = 0, prof_a4 = 0;
-#endif
-#ifdef MVP_EMD_PROFILE
-  const long long t_loop0 = __builtin_readcyclecounter();
-#endif
-#ifdef MVP_EMD_CLOUDTIME
-  const long long ct0 = wall_clock64();
-  int ct_u[6] = {0, 0, 0, 0, 0, 0};
-  long long ct_t[6] = {0, 0, 0, 0, 0, 0}, ct_b[6] = {0, 0, 0, 0, 0, 0};
-#endif
+  EMD_PROF(EmdProbe pr;)
+  EMD_CTIME(const long long ct0 = wall_clock64();)
   // The round loop, instantiated twice -- GM = false: bid atomics + two all-gathers per round; GM = true: gathered-bid
   // rounds -- so that each mode gets its own register allocation (one loop with a run-time mode: 98 -> 124 VGPRs and
   // twice the scalar spills in BOTH modes).  Returns 0 when the rounds are over (or the workgroup has nothing left to
@@ -346,19 +246,7 @@ __device__ __forceinline__ int emd_lean_body(LeanShared &sh, const int cloud, co
   for (; it < iters; ++it) {
     int sw = 0;   // 2: gathered-bid rounds from the next round on; 3: back to the plain rounds (member 0 alone)
     if (Utot == 0) break;
-#ifdef MVP_EMD_PROFILE
-    if (cloud == 0 && wg == 0 && t == 0 && (it == 25 || it == 50 || it == 100 || it == 150 || it == 250 || it == 500 || it == 750 ||
-                                           it == 1000 || it == 1500 || it == 2000 || it == 2500 || it == iters - 1))
-      printf("head cloud 0: round %d starts at %lld cycles, unassigned %d\n", it, __builtin_readcyclecounter() - t_loop0, Utot);
-#endif
-#ifdef MVP_EMD_CLOUDTIME
-    {
-      const int marks[6] = {150, 200, 300, 500, 1000, 2000};
-#pragma unroll
-      for (int q = 0; q < 6; ++q)
-        if (it == marks[q]) { ct_u[q] = Utot; ct_t[q] = wall_clock64() - ct0; ct_b[q] = n_bids; }
-    }
-#endif
+    EMD_PROF(pr.head(false, cloud, wg, it, iters, Utot);)
     // gathered-bid round: every member's list length (scalar registers), this member's first position in the
     // cloud-wide order, and the heartbeat -- "every store this member issued in earlier rounds is performed" (the
     // previous settle ended with a drain); the others' settle of THIS round waits for it
@@ -366,11 +254,8 @@ __device__ __forceinline__ int emd_lean_body(LeanShared &sh, const int cloud, co
     if constexpr (WB != 1) {
       if constexpr (GM) {
         ++eg;
-#ifdef MVP_EMD_GMTIME
-        if (gm_prev) GMT(0) else gm_prev = __builtin_readcyclecounter();   // [0] end of the last round's bookkeeping -> this round's start
-        gmt[15] += 1;
-        GMT(14) GMT(14)   // [14] = two stamps back to back (calibration)
-#endif
+        EMD_GMTIME(if (gm_prev) GMT(0) else gm_prev = __builtin_readcyclecounter();)   // [0] end of the last round's bookkeeping -> this round's start
+        EMD_GMTIME(gmt[15] += 1; GMT(14) GMT(14))   // [14] = two stamps back to back (calibration)
         goff = 0;
         {
           const int cv = s_gc[gcur][lane & (kMaxCluster - 1)];   // (one LDS read; the sum is scalar work)
@@ -378,11 +263,7 @@ __device__ __forceinline__ int emd_lean_body(LeanShared &sh, const int cloud, co
           for (int w = 0; w + 1 < WM; ++w)
             if (w < wg) goff += __builtin_amdgcn_readlane(cv, w);
         }
-#ifdef MVP_EMD_HBTOP
-        if (t == 0) {
-#else
         if (t == 0 && s_gc[gcur][wg] == 0) {   // (a member with bidders: its last bid of the round raises the word)
-#endif
           u64 *hb = bid_area + (size_t)(eg & 1u) * kGStride + 2 * kGCap + wg;
           if (same_xcd) __hip_atomic_store(hb, (u64)eg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
           else __hip_atomic_store(hb, (u64)eg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -397,10 +278,8 @@ __device__ __forceinline__ int emd_lean_body(LeanShared &sh, const int cloud, co
     // order only.
     const int tpu = -Utot;   // (resolved inside emd_precedes: only equal values ever need it)
 
-#ifdef MVP_EMD_PROFILE
-    const long long tp0 = __builtin_readcyclecounter();
-    if (prof_prev4) prof_gap += tp0 - prof_prev4;
-#endif
+    EMD_PROF(const long long tp0 = __builtin_readcyclecounter();
+             if (pr.prof_prev4) pr.prof_gap += tp0 - pr.prof_prev4;)
     // A bid = one returning 64-bit atomic max on the object's key; the value
     // it returns is examined one bid later (or after the loop), so the wave
     // never waits for it.
@@ -411,11 +290,9 @@ __device__ __forceinline__ int emd_lean_body(LeanShared &sh, const int cloud, co
 #include "emd_lean_bid.inc"
     }
     const int nxt = cur ^ 1;
-#ifdef MVP_EMD_PROFILE
-    const long long tp1 = __builtin_readcyclecounter();
-    long long tp2 = tp1, tp3 = tp1;
-    if (lane == 0) s_wbusy[wave] = (int)(tp1 - tp0);
-#endif
+    EMD_PROF(const long long tp1 = __builtin_readcyclecounter();
+             long long tp2 = tp1, tp3 = tp1;
+             if (lane == 0) pl.s_wbusy[wave] = (int)(tp1 - tp0);)
     if constexpr (!GM) {
 #include "emd_lean_round_plain.inc"
     } else {
@@ -449,16 +326,14 @@ __device__ __forceinline__ int emd_lean_body(LeanShared &sh, const int cloud, co
     }
   }
   if (ret_early) return 0;
-#ifdef MVP_EMD_PROFILE
-  if (clustered && !aborted) {  // cost of the bare all-gather
-    const long long tg0 = __builtin_readcyclecounter();
-    for (int g = 0; g < 256; ++g)
-      if (!emd_cluster_gather_n<WM>(slots, W, wg, ++epoch, &s_nchg, &s_nchg, s_gout, &s_abort, same_xcd)) break;
-    if (t == 0 && cloud < 2 && wg == 0)
-      printf("cloud %d: bare cluster all-gather %lld cycles each (W = %d, same_xcd %d)\n", cloud,
-             (__builtin_readcyclecounter() - tg0) / 256, W, (int)same_xcd);
-  }
-#endif
+  EMD_PROF(if (clustered && !aborted) {   // cost of the bare all-gather
+             const long long tg0 = __builtin_readcyclecounter();
+             for (int g = 0; g < 256; ++g)
+               if (!emd_cluster_gather_n<WM>(slots, W, wg, ++epoch, &s_nchg, &s_nchg, s_gout, &s_abort, same_xcd)) break;
+             if (t == 0 && cloud < 2 && wg == 0)
+               printf("cloud %d: bare cluster all-gather %lld cycles each (W = %d, same_xcd %d)\n", cloud,
+                      (__builtin_readcyclecounter() - tg0) / 256, W, (int)same_xcd);
+           })
   if (stop_cnt >= 0) {
     // ---- stopped before round it_stop: leave the lists for the next launch, as the first kernel
     // left them for this one (the prices, owners and bid hints are in the scratch already).  The
@@ -477,9 +352,7 @@ __device__ __forceinline__ int emd_lean_body(LeanShared &sh, const int cloud, co
       atomicAdd(reinterpret_cast<unsigned long long *>(&st2[1]), (unsigned long long)n_bids);
       if (s_err) rs->err = 1;
       rs->cnt[wg] = stop_cnt;
-#ifdef MVP_EMD_CLOUDTIME
-      if (wg == 0) sc.chg[(size_t)kMaxCluster * kChgCap - 64 + (min(stop_it, 3900) >> 6)] = ((u64)W << 48) | ((u64)Utot << 32) | (u64)(unsigned)(wall_clock64() - ct0);
-#endif
+      EMD_CTIME(if (wg == 0) sc.chg[(size_t)kMaxCluster * kChgCap - 64 + (min(stop_it, 3900) >> 6)] = emd_ctime_word(W, Utot, wall_clock64() - ct0);)
       if (wg == 0) {
         rs->utot = Utot;
         rs->nlists = clustered ? W : 1;
@@ -508,28 +381,16 @@ __device__ __forceinline__ int emd_lean_body(LeanShared &sh, const int cloud, co
     }
     return 0;
   }
-#ifdef MVP_EMD_CLOUDTIME
-  if (wg == 0 && t == 0)   // 100 MHz constant clock
-    sc.chg[(size_t)kMaxCluster * kChgCap - 64 + 63] = ((u64)W << 48) | (u64)(unsigned)(wall_clock64() - ct0);
-#endif
+  EMD_CTIME(if (wg == 0 && t == 0) sc.chg[(size_t)kMaxCluster * kChgCap - 64 + 63] = emd_ctime_word(W, 0, wall_clock64() - ct0);)   // 100 MHz constant clock
   if (aborted) {
-    // A cluster wait ran into its bound (the members were not co-resident for
-    // tens of seconds).  Fail loudly: NaN distances, -1 assignments.
     if (t == 0) stats[0] = -2;
-#ifndef MVP_EMD_STUCKDUMP
-    for (int j = t; j < n; j += kEmdThreads) {
-      dist[j] = __builtin_nanf("");
-      ass[j] = -1;
-    }
-#endif
+    emd_abort_fill(dist, ass, n);
     return 0;
   }
-#ifdef MVP_EMD_GMTIME
-  if (t == 0 && wg == 0) {
-    for (int k = 0; k < 16; ++k) sc.chg[(size_t)kMaxCluster * kChgCap - 128 + k] = (u64)gmt[k];
-    sc.chg[(size_t)kMaxCluster * kChgCap - 128 + 16] = (u64)W;
-  }
-#endif
+  EMD_GMTIME(if (t == 0 && wg == 0) {
+               for (int k = 0; k < 16; ++k) sc.chg[(size_t)kMaxCluster * kChgCap - 128 + k] = (u64)gmt[k];
+               sc.chg[(size_t)kMaxCluster * kChgCap - 128 + 16] = (u64)W;
+             })
   if (t == 0) {
     // rounds: added to the first kernel's count; an internal error drives the sum far below zero
     if (wg == 0) {
@@ -540,39 +401,7 @@ __device__ __forceinline__ int emd_lean_body(LeanShared &sh, const int cloud, co
     }
     if (s_err) atomicAdd(reinterpret_cast<unsigned long long *>(&stats[0]), (unsigned long long)(-(1ll << 40)));
     atomicAdd(reinterpret_cast<unsigned long long *>(&stats[1]), (unsigned long long)n_bids);
-#ifdef MVP_EMD_PROFILE
-    if (cloud < 2)
-      printf("cloud %d wg %d per wave-mode bid: seed %llu cycles, visits %llu cycles in %.2f steps folding %.1f candidates, rest (enumeration, finish) %llu\n", cloud, wg,
-             s_hist2[0] / (s_hist[10] + 1), s_hist2[1] / (s_hist[10] + 1), (double)s_hist2[2] / (double)(s_hist[10] + 1), (double)s_hist2[3] / (double)(s_hist[10] + 1),
-             (s_hist[12] - s_hist2[0] - s_hist2[1]) / (s_hist[10] + 1));
-    if (cloud < 2)
-      printf("cloud %d wg %d price-bound refreshes after round 100: %llu\n", cloud, wg, s_hist2[0] >> 40);
-    if (cloud == 0 && wg == 0)
-      for (int k = 0; k < 2; ++k) {
-        const double c = (double)s_slow[k][0] + 1e-9;
-        printf("cloud 0 wg 0 searches %s 10k cycles: seed threshold %.3f cell widths, of which %.3f loose (seed - final)\n", k ? ">=" : "<",
-               s_loose[k][1] / c, s_loose[k][0] / c);
-        printf("cloud 0 wg 0 searches %s 10k cycles: %llu | mean sub-box %.0f cells, visited %.1f, visit steps %.2f, extra member iterations %.2f, folds %.1f, seed %.0f cycles, visits %.0f cycles\n",
-               k ? ">=" : "<", s_slow[k][0], s_slow[k][1] / c, s_slow[k][2] / c, s_slow[k][3] / c, s_slow[k][4] / c, s_slow[k][5] / c, s_slow[k][6] / c, s_slow[k][7] / c);
-      }
-    if (cloud < 2)
-      printf("cloud %d wg %d gathered rounds (thread 0, %lld): contest check %lld, settle body %lld, drain %lld, to barrier end %lld cycles per round; flagged %.2f contested %.3f per round\n", cloud, wg, prof_an,
-             prof_a1 / (prof_an + 1), prof_a2 / (prof_an + 1), prof_a3 / (prof_an + 1), prof_a4 / (prof_an + 1), (double)(s_hist2[3] >> 32) / (double)(prof_an + 1), (double)(s_hist2[2] >> 32) / (double)(prof_an + 1));
-    if (cloud < 2 && false)
-      printf("cloud %d wg %d Assign (thread 0, %lld samples): loads done at %lld cycles, eviction handled at %lld (sum over winning rounds / all), body done at %lld, phase %lld\n", cloud, wg, prof_an, prof_a1 / (prof_an + 1), prof_a2 / (prof_an + 1), prof_a3 / (prof_an + 1), prof_a4 / (prof_an + 1));
-    if (cloud < 2)
-      printf("cloud %d wg %d tail rounds %llu: bidders/round %.1f, busiest wave %llu cycles/round, mean wave %llu\n", cloud, wg, s_hist[15],
-             (double)prof_u / (double)(s_hist[15] + 1), s_hist[13] / (s_hist[15] + 1), s_hist[14] / (s_hist[15] + 1));
-    if (cloud < 2)
-      printf("cloud %d wg %d wave-mode bids after round 100: %llu, mean cycles %llu, mean sub-box cells %llu, mean cells visited %llu, linear %llu | <2k %llu <4k %llu <8k %llu <16k %llu <32k %llu <64k %llu <128k %llu more %llu\n",
-             cloud, wg, s_hist[10], s_hist[12] / (s_hist[10] + 1), s_hist[8] / (s_hist[10] + 1), s_hist[9] / (s_hist[10] + 1), s_hist[11],
-             s_hist[0], s_hist[1], s_hist[2], s_hist[3], s_hist[4], s_hist[5], s_hist[6], s_hist[7]);
-    if (cloud < 2)
-      printf("cloud %d wg %d: rounds %lld bids %lld alarms %lld rebalances %lld | cycles bid %lld sync1 %lld assign %lld sync2 %lld gap %lld\n",
-             cloud, wg, n_rounds, n_bids, n_alarm, n_rebal, cyc_bid, cyc_sync1, cyc_assign, cyc_sync2, prof_gap);
-    if (cloud < 2)
-      printf("cloud %d wg %d: sync2 = store drain %lld + closing gather %lld + list bookkeeping %lld + bound fetch (rest)\n", cloud, wg, prof_drain, prof_gather, prof_pg1);
-#endif
+    EMD_PROF(emd_probe_report(true, pl, pr, cloud, wg, n_rounds, n_bids);)
   }
   // ---------------- CalcDist (emd_cuda.cu:217-226); slots -> object indices
   __syncthreads();

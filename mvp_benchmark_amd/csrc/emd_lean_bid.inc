@@ -14,10 +14,7 @@
       const int j = rb.x;
       const float qx = ra.x, qy = ra.y, qz = ra.z;
       const int p1 = rb.y, p2 = rb.z;
-#ifdef MVP_EMD_PROFILE
-      const long long tb0 = __builtin_readcyclecounter();
-      int prof_cells = 0;
-#endif
+      EMD_PROF(EmdBidProbe bp;)
       const int hc = __float_as_int(ra.w);   // home chunk (emd_index.h)
       BidState st;
       st.b1 = -1e9f;
@@ -27,44 +24,11 @@
       st.bp = 0.f;
       unsigned short *wl = w_list[wave];
       int nsub = 0;          // leaves tested (statistics)
-#ifdef MVP_EMD_PROFILE
-      long long tb1 = tb0;
-      float prof_tm_seed = 0.f;
-      long long t_visit = 0;
-      int n_visit = 0, prof_fold = 0, prof_more = 0;
-#endif
 #define EMD_SEARCH_FOLD(m_, v_, slot_, price_) emd_fold<GM>(st, m_, v_, slot_, n, tpu, sc.perm, price_)
 #include "emd_search_wave.inc"
 #undef EMD_SEARCH_FOLD
       (void)nsub;
-#ifdef MVP_EMD_PROFILE
-      if (lane == 0 && it >= 100) {
-        const long long d = __builtin_readcyclecounter() - tb0;
-        int bkt = 0;
-        while (bkt < 7 && d >= (2000ll << bkt)) ++bkt;
-        atomicAdd(&s_hist[bkt], 1ull);
-        atomicAdd(&s_hist[8], (unsigned long long)nsub);
-        atomicAdd(&s_hist[9], (unsigned long long)prof_cells);
-        atomicAdd(&s_hist[10], 1ull);
-        if (linear) atomicAdd(&s_hist[11], 1ull);
-        atomicAdd(&s_hist[12], (unsigned long long)d);
-        atomicAdd(&s_hist2[0], (unsigned long long)(tb1 - tb0));
-        atomicAdd(&s_hist2[1], (unsigned long long)t_visit);
-        atomicAdd(&s_hist2[2], (unsigned long long)n_visit);
-        atomicAdd(&s_hist2[3], (unsigned long long)prof_fold);
-        atomicAdd(&s_loose[d >= 10000 ? 1 : 0][0], prof_tm_seed - ((3.0f - st.b2) + kMargin));
-        atomicAdd(&s_loose[d >= 10000 ? 1 : 0][1], prof_tm_seed);
-        unsigned long long *sl = s_slow[d >= 10000 ? 1 : 0];
-        atomicAdd(&sl[0], 1ull);
-        atomicAdd(&sl[1], (unsigned long long)nsub);
-        atomicAdd(&sl[2], (unsigned long long)prof_cells);
-        atomicAdd(&sl[3], (unsigned long long)n_visit);
-        atomicAdd(&sl[4], (unsigned long long)prof_more);
-        atomicAdd(&sl[5], (unsigned long long)prof_fold);
-        atomicAdd(&sl[6], (unsigned long long)(tb1 - tb0));
-        atomicAdd(&sl[7], (unsigned long long)t_visit);
-      }
-#endif
+      EMD_PROF(if (lane == 0 && it >= 100) bp.done(pl, nsub, linear, (3.0f - st.b2) + kMargin);)
       if (st.bk < 0) {  // cannot happen (>= 2 objects always survive); never index with -1
         if (lane == 0) s_err = 1;
         st.bk = 0;
@@ -72,7 +36,7 @@
       }
       if (lane == 0) {
         const float inc = st.b1 - st.b2 + eps;
-        st_person_hi(j, st.bk, st.bk, st.b2k, inc);
+        sa.st_person_hi(j, st.bk, st.bk, st.b2k, inc);
         if constexpr (GM) {
           // The bid as a granule at this bidder's position of the cloud-wide order: two 8-byte words, each with a
           // tag of the round -- {increment | object 14 | bidder 14 | tag 4}, {the object's new price | second-best
@@ -96,11 +60,7 @@
           // -- the previous settle ended with a drain): raised with the member's last bid.  It is what the others
           // spin on (W words per poll instead of every bid: polling the bids themselves by every waiting wave of 256
           // CUs saturated the L2 and doubled the round); only a hint for the bids -- each carries its own tags.
-#ifdef MVP_EMD_HBTOP
-          if (false) {
-#else
           if (atomicAdd(&s_pub, 1) == U - 1) {
-#endif
             u64 *hb = bid_area + (size_t)(eg & 1u) * kGStride + 2 * kGCap + wg;
             if (same_xcd) __hip_atomic_store(hb, (u64)eg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             else __hip_atomic_store(hb, (u64)eg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

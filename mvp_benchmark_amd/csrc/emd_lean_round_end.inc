@@ -2,26 +2,20 @@
 // every name used here is a local of emd_lean_body / of the `rounds` lambda (GM = gathered-bid rounds).
     // ---------------- end of round: next list sizes + refreshed price bounds
     if (clustered) {
-#ifdef MVP_EMD_PROFILE
-      long long tpd = tp3, tpg2 = tp3;
-#endif
+      EMD_PROF(long long tpd = tp3, tpg2 = tp3;)
       Utot = 0;
       bool overflow = false;
       int cntw[WM], chgw[WM];  // (the same for every lane: kept in scalar registers, the arithmetic on them is SALU work)
       if constexpr (!GM) {
-#ifdef MVP_EMD_PROFILE
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        tpd = __builtin_readcyclecounter();
-#endif
+        EMD_PROF(asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                 tpd = __builtin_readcyclecounter();)
         if (!emd_cluster_gather_n<WM>(slots, W, wg, ++epoch, &s_cnt[nxt], &s_nchg, s_gout, &s_abort, same_xcd)) {
           aborted = true;
           break;
         }
-#ifdef MVP_EMD_PROFILE
-        tpg2 = __builtin_readcyclecounter();
-        prof_drain += tpd - tp3;
-        prof_gather += tpg2 - tpd;
-#endif
+        EMD_PROF(tpg2 = __builtin_readcyclecounter();
+                 pr.prof_drain += tpd - tp3;
+                 pr.prof_gather += tpg2 - tpd;)
 #pragma unroll
         for (int w = 0; w < WM; ++w) {
           cntw[w] = w < W ? __builtin_amdgcn_readfirstlane((int)s_gout[2 * w]) : 0;
@@ -58,7 +52,7 @@
       if (__builtin_expect(Utot > 0 && Utot <= kLeanSoloMax && it + 1 < iters, 0)) {
         // ---- hand everything to member 0 (lists of <= kSoloMax persons live
         // in LDS only: publish the person ids; their records are in memory)
-        if (wg != 0 && t < cntw[wg]) st_i32(my_ulist + t, s_ri[nxt][t].x);
+        if (wg != 0 && t < cntw[wg]) sa.st_i32(my_ulist + t, s_ri[nxt][t].x);
         if (!emd_cluster_gather_n<WM>(slots, W, wg, ++epoch, &s_nchg, &s_nchg, s_gout, &s_abort, same_xcd)) {
           aborted = true;
           break;
@@ -74,8 +68,8 @@
           if (idx >= 0 && idx < cntw[w]) {
             const int jj = __hip_atomic_load(sc.ulist + (size_t)w * 2 * n + idx, __ATOMIC_RELAXED,
                                              __HIP_MEMORY_SCOPE_AGENT);
-            const float4 pa = ld_person(jj, 0);
-            const float4 pb = ld_person(jj, 1);
+            const float4 pa = sa.ld_person(jj, 0);
+            const float4 pb = sa.ld_person(jj, 1);
             const int pos = atomicAdd(&s_cnt[nxt], 1);
             s_rq[nxt][pos] = pa;
             s_ri[nxt][pos] = make_int4(jj, __float_as_int(pb.y), __float_as_int(pb.z), 0);
@@ -115,7 +109,7 @@
           int *dead = my_ulist + (size_t)cur * n;   // this round's list: no longer read
           for (int i = t; i < my_exc; i += kEmdThreads) {
             const int pos = my_cnt - my_exc + i;
-            st_i32(dead + i, s_ri[nxt][pos].x);
+            sa.st_i32(dead + i, s_ri[nxt][pos].x);
           }
           if (!emd_cluster_gather_n<WM>(slots, W, wg, ++epoch, &s_nchg, &s_nchg, s_gout, &s_abort, same_xcd)) {
             aborted = true;
@@ -131,8 +125,8 @@
               p -= exc[w];
             }
             const int pos = my_cnt + i;
-            const float4 pa = ld_person(jj, 0);
-            const float4 pb = ld_person(jj, 1);
+            const float4 pa = sa.ld_person(jj, 0);
+            const float4 pb = sa.ld_person(jj, 1);
             s_rq[nxt][pos] = pa;
             s_ri[nxt][pos] = make_int4(jj, __float_as_int(pb.y), __float_as_int(pb.z), 0);
           }
@@ -140,15 +134,11 @@
           __syncthreads();
 #pragma unroll
           for (int w = 0; w < WM; ++w) cntw[w] = w < W ? base + (w < rem ? 1 : 0) : 0;   // (every list is at its even share now)
-#ifdef MVP_EMD_PROFILE
-          n_rebal += 1;
-#endif
+          EMD_PROF(pr.n_rebal += 1;)
         }
       }
-#ifdef MVP_EMD_PROFILE
-      const long long tpb = __builtin_readcyclecounter();
-      prof_pg1 += tpb - tpg2;
-#endif
+      EMD_PROF(const long long tpb = __builtin_readcyclecounter();
+               pr.prof_pg1 += tpb - tpg2;)
       // the nodes' price bounds follow their leaves' (one lane per node, the last wave -- it seldom has a bidder; LDS
       // only, before this round's re-scans land: a bound that lags a round is still a bound)
       if (t >= kEmdThreads - kMaxNodes) emd_node_price(l_lo, n_lo, t - (kEmdThreads - kMaxNodes), nleaf);
@@ -157,10 +147,10 @@
         const int e0 = leaf << lshift, e1 = e0 + (1 << lshift);
         float pv[16], pm = __builtin_inff();
 #pragma unroll
-        for (int k = 0; k < 16; ++k) pv[k] = ld_price(e0 + k);
+        for (int k = 0; k < 16; ++k) pv[k] = sa.ld_price(e0 + k);
 #pragma unroll
         for (int k = 0; k < 16; ++k) pm = __builtin_fminf(pm, pv[k]);
-        for (int s2 = e0 + 16; s2 < e1; ++s2) pm = __builtin_fminf(pm, ld_price(s2));
+        for (int s2 = e0 + 16; s2 < e1; ++s2) pm = __builtin_fminf(pm, sa.ld_price(s2));
         l_lo[leaf].w = pm;
       };
       if constexpr (GM) {
@@ -242,18 +232,12 @@
         if (idx < own_cnt) {
           const int leaf = s_own_chg[idx];
           float pm = __builtin_inff();
-          for (int s2 = leaf << lshift; s2 < ((leaf + 1) << lshift); ++s2) pm = __builtin_fminf(pm, ld_price(s2));
+          for (int s2 = leaf << lshift; s2 < ((leaf + 1) << lshift); ++s2) pm = __builtin_fminf(pm, sa.ld_price(s2));
           l_lo[leaf].w = pm;
         }
       }
     }
-#ifdef MVP_EMD_PROFILE
-    const long long tp4 = __builtin_readcyclecounter();
-    prof_prev4 = tp4;
-    cyc_bid += tp1 - tp0; cyc_sync1 += tp2 - tp1; cyc_assign += tp3 - tp2; cyc_sync2 += tp4 - tp3;
-    if (t == 0 && it >= 100) {
-      int mx = 0, sm = 0;
-      for (int w = 0; w < kEmdWaves; ++w) { mx = max(mx, s_wbusy[w]); sm += s_wbusy[w]; }
-      s_hist[13] += mx; s_hist[14] += sm / kEmdWaves; s_hist[15] += 1; prof_u += U;
-    }
-#endif
+    EMD_PROF(const long long tp4 = __builtin_readcyclecounter();
+             pr.prof_prev4 = tp4;
+             pr.cyc_bid += tp1 - tp0; pr.cyc_sync1 += tp2 - tp1; pr.cyc_assign += tp3 - tp2; pr.cyc_sync2 += tp4 - tp3;
+             if (t == 0 && it >= 100) pr.round_end(pl, U);)

@@ -55,18 +55,14 @@
     // the owner map: the gathered-bid rounds keep it (every member's view); after plain rounds it is read from the
     // objects' records (every store of the last round is performed: the round ended with a drain and a barrier)
     if (!owners_in_lds)
-      for (int s2 = t; s2 < n; s2 += kEmdThreads) s_owner[s2] = (unsigned short)ld_ostate(s2).z;
+      for (int s2 = t; s2 < n; s2 += kEmdThreads) s_owner[s2] = (unsigned short)sa.ld_ostate(s2).z;
     __syncthreads();
   }
   unsigned short *wl = w_list[wv];
   const int sl16 = lane & 15;
-#ifdef MVP_EMD_PROFILE
-  long long fw_bid = 0, fw_wait = 0, fw_settle = 0, fw_close = 0, fw_rounds = 0, fw_mybids = 0, fw_search = 0;
-#endif
+  EMD_PROF(long long fw_bid = 0, fw_wait = 0, fw_settle = 0, fw_close = 0, fw_rounds = 0, fw_mybids = 0, fw_search = 0;)
   for (; it < iters; ++it) {
-#ifdef MVP_EMD_PROFILE
-    const long long fw0 = __builtin_readcyclecounter();
-#endif
+    EMD_PROF(const long long fw0 = __builtin_readcyclecounter();)
     const int U = __builtin_amdgcn_readfirstlane(f_act[it % 3]);
     if (U == 0) break;
     Utot = U;
@@ -96,23 +92,14 @@
         const float qx = fqx[p], qy = fqy[p], qz = fqz[p];
         const int hc = fhc[p], p1 = fp1[p], p2 = fp2[p];
         int nsub = 0;
-#ifdef MVP_EMD_PROFILE
-        long long tb1 = 0, t_visit = 0;
-        float prof_tm_seed = 0.f;
-        int n_visit = 0, prof_fold = 0, prof_more = 0, prof_cells = 0;
-#endif
+        EMD_PROF(EmdBidProbe bp;)
 #define EMD_SEARCH_FOLD(m_, v_, slot_, price_) emd_fold<true>(st, m_, v_, slot_, n, tpu, sc.perm, price_)
 #include "emd_search_wave.inc"
 #undef EMD_SEARCH_FOLD
         (void)nsub;
         (void)linear;
-#ifdef MVP_EMD_PROFILE
-        (void)tb1; (void)t_visit; (void)prof_tm_seed; (void)n_visit; (void)prof_fold; (void)prof_more; (void)prof_cells;
-#endif
-#ifdef MVP_EMD_PROFILE
-        fw_search += __builtin_readcyclecounter() - fw0;
-        fw_mybids += 1;
-#endif
+        EMD_PROF(fw_search += __builtin_readcyclecounter() - fw0;
+                 fw_mybids += 1;)
         if (st.bk < 0) {  // cannot happen (>= 2 objects always survive); never index with -1
           if (lane == 0) s_err = 1;
           st.bk = 0;
@@ -123,18 +110,18 @@
         b2ko[p] = st.b2k;
         inco[p] = inc;
         npo[p] = st.bp + inc;
-        pwo[p] = ld_price((st.bk & ~15) + sl16);   // the leaf's prices as they are during Bid (used if the bid wins)
+        pwo[p] = sa.ld_price((st.bk & ~15) + sl16);   // the leaf's prices as they are during Bid (used if the bid wins)
         // ... and the record of the object's owner (the map does not change during Bid), requested NOW: if the bid wins --
         // nearly always -- the evicted owner's point and hints have arrived by the time the barrier opens
         if (!last) {
           prevo[p] = __builtin_amdgcn_readfirstlane((int)s_owner[st.bk]);
           if (prevo[p] != 0xFFFF) {
-            pa[p] = ld_person(prevo[p], 0);
-            pb[p] = ld_person(prevo[p], 1);
+            pa[p] = sa.ld_person(prevo[p], 0);
+            pb[p] = sa.ld_person(prevo[p], 1);
           }
         }
         if (lane == 0) {
-          st_person_hi(fj[p], st.bk, st.bk, st.b2k, inc);
+          sa.st_person_hi(fj[p], st.bk, st.bk, st.b2k, inc);
           s_bj[pos] = fj[p];
           s_bo[pos] = st.bk;
           s_binc[pos] = inc;
@@ -144,21 +131,17 @@
         s_bj[pos] = -1;
       }
     }
-#ifdef MVP_EMD_PROFILE
-    const long long fw1 = __builtin_readcyclecounter();
-#endif
+    EMD_PROF(const long long fw1 = __builtin_readcyclecounter();)
     lds_barrier();
-#ifdef MVP_EMD_PROFILE
-    const long long fw2 = __builtin_readcyclecounter();
-#endif
+    EMD_PROF(const long long fw2 = __builtin_readcyclecounter();)
     if (last) {
       // the forced last round (emd_cuda.cu:201-212): every bidder takes the object it bid on
 #pragma unroll
       for (int p = 0; p < P; ++p)
         if (fj[p] >= 0 && lane == 0) {
-          st_ostate(bko[p], fj[p]);
-          st_i32(&ass[fj[p]], bko[p]);
-          st_f32(&sc.obj[bko[p]].w, npo[p]);
+          sa.st_ostate(bko[p], fj[p]);
+          sa.st_i32(&ass[fj[p]], bko[p]);
+          sa.st_f32(&sc.obj[bko[p]].w, npo[p]);
         }
       break;
     }
@@ -195,10 +178,10 @@
             s_owner[bk] = (unsigned short)fj[p];
             l_lo[leaf].w = pm;
             n_lo[leaf / kNodeFan].w = nm;
-            st_f32(&sc.obj[bk].w, npo[p]);
-            st_ostate(bk, fj[p]);
-            st_i32(&ass[fj[p]], bk);
-            if (prev != 0xFFFF) st_i32(&ass[prev], -1);
+            sa.st_f32(&sc.obj[bk].w, npo[p]);
+            sa.st_ostate(bk, fj[p]);
+            sa.st_i32(&ass[fj[p]], bk);
+            if (prev != 0xFFFF) sa.st_i32(&ass[prev], -1);
           }
           if (prev != 0xFFFF) {   // the evicted owner bids next round, from this position
             fj[p] = prev;
@@ -223,17 +206,11 @@
       reinterpret_cast<int4 *>(f_cnt[(it + 1) & 1])[lane] = make_int4(0, 0, 0, 0);
       if (lane == 0) f_act[(it + 2) % 3] = 0;
     }
-#ifdef MVP_EMD_PROFILE
-    const long long fw3 = __builtin_readcyclecounter();
-#endif
+    EMD_PROF(const long long fw3 = __builtin_readcyclecounter();)
     __syncthreads();   // (also: the stores are performed -- the next searches read the prices -- and the record has arrived)
-#ifdef MVP_EMD_PROFILE
-    const long long fw4 = __builtin_readcyclecounter();
-    fw_bid += fw1 - fw0; fw_wait += fw2 - fw1; fw_settle += fw3 - fw2; fw_close += fw4 - fw3; fw_rounds += 1;
-#endif
+    EMD_PROF(const long long fw4 = __builtin_readcyclecounter();
+             fw_bid += fw1 - fw0; fw_wait += fw2 - fw1; fw_settle += fw3 - fw2; fw_close += fw4 - fw3; fw_rounds += 1;)
   }
-#ifdef MVP_EMD_PROFILE
-  if (cloud < 2 && lane == 0 && (wv == 0 || wv == 5) && fw_rounds > 0)
-    printf("few-bidder rounds cloud %d wave %d: %lld rounds from round %d | per round: bid phase %lld, wait at barrier %lld, settle %lld, closing barrier (stores + record) %lld cycles | this wave: %lld bids, search %lld cycles each\n",
-           cloud, wv, fw_rounds, (int)(it - fw_rounds), fw_bid / fw_rounds, fw_wait / fw_rounds, fw_settle / fw_rounds, fw_close / fw_rounds, fw_mybids, fw_search / (fw_mybids + 1));
-#endif
+  EMD_PROF(if (cloud < 2 && lane == 0 && (wv == 0 || wv == 5) && fw_rounds > 0)
+             printf("few-bidder rounds cloud %d wave %d: %lld rounds from round %d | per round: bid phase %lld, wait at barrier %lld, settle %lld, closing barrier (stores + record) %lld cycles | this wave: %lld bids, search %lld cycles each\n",
+                    cloud, wv, fw_rounds, (int)(it - fw_rounds), fw_bid / fw_rounds, fw_wait / fw_rounds, fw_settle / fw_rounds, fw_close / fw_rounds, fw_mybids, fw_search / (fw_mybids + 1));)

@@ -18,24 +18,7 @@
             if (__all(x == (u64)eg)) break;
             if (spins >= kSpinLimit) {
               if (lane == 0) s_abort = 1;
-#ifdef MVP_EMD_STUCKDUMP
-              if (wave == 0) {
-                int *dd = ass + wg * 32;
-                if (lane < W) dd[lane] = (int)x;
-                if (lane == 8) dd[8] = (int)eg;
-                if (lane == 9) dd[9] = it;
-                if (lane == 10) dd[10] = Utot;
-                if (lane == 11) dd[11] = U;
-                if (lane == 12) dd[12] = s_pub;
-                if (lane == 13) dd[13] = goff;
-                if (lane == 14) dd[14] = gi;
-                if (lane == 15) dd[15] = 777;
-                if (lane >= 16 && lane < 16 + WM) dd[lane] = s_gc[gcur][lane - 16];
-              }
-#endif
-#if defined(MVP_EMD_PROFILE) || defined(MVP_EMD_STUCK)
-              if (lane < W) printf("cloud %d wg %d wave %d: member word %d stuck at %llu, want %u (it %d Utot %d U %d goff %d gi %d pub %d)\n", cloud, wg, wave, lane, x, eg, it, Utot, U, goff, gi, s_pub);
-#endif
+              EMD_PROF(if (lane < W) printf("cloud %d wg %d wave %d: member word %d stuck at %llu, want %u (it %d Utot %d U %d goff %d gi %d pub %d)\n", cloud, wg, wave, lane, x, eg, it, Utot, U, goff, gi, s_pub);)
               break;
             }
             __builtin_amdgcn_s_sleep(1);
@@ -52,9 +35,7 @@
             if (__all(ok)) break;
             if (spins >= kSpinLimit) {
               if (lane == 0) s_abort = 1;
-#if defined(MVP_EMD_PROFILE) || defined(MVP_EMD_STUCK)
-              if (!ok) printf("cloud %d wg %d: bid %d stuck: %llx %llx, want tags %u %u (it %d Utot %d U %d goff %d)\n", cloud, wg, t, g0, g1, T4, T6, it, Utot, U, goff);
-#endif
+              EMD_PROF(if (!ok) printf("cloud %d wg %d: bid %d stuck: %llx %llx, want tags %u %u (it %d Utot %d U %d goff %d)\n", cloud, wg, t, g0, g1, T4, T6, it, Utot, U, goff);)
               break;
             }
             __builtin_amdgcn_s_sleep(1);
@@ -84,8 +65,8 @@
           if (!last) {
             prev = s_owner[go];
             if (prev != 0xFFFF && t % W == wg) {
-              pa = ld_person(prev, 0);
-              pb = ld_person(prev, 1);
+              pa = sa.ld_person(prev, 0);
+              pb = sa.ld_person(prev, 1);
             }
           }
         }
@@ -96,17 +77,13 @@
           aborted = true;
           break;
         }
-#ifdef MVP_EMD_PROFILE
-        tp2 = __builtin_readcyclecounter();
-#endif
+        EMD_PROF(tp2 = __builtin_readcyclecounter();)
         int rec_pos = -1;
         // Bids for an object that got more than one bid (~0.3 per round at the headline): the wave settles one of
         // them at a time -- the maximal increment bid on the object, then the highest bidder inside its 1e-6 band
         // (emd_cuda.cu:181-194), over all of the round's bids, four per lane.
         int contested = 0;   // 1: another bid wins my object
-#ifdef MVP_EMD_PROFILE
-        const long long tq0 = __builtin_readcyclecounter();
-#endif
+        EMD_PROF(const long long tq0 = __builtin_readcyclecounter();)
         if (wave * kWave < Utot && !last) {
           bool flagged = false;
           if (t < Utot) {
@@ -115,9 +92,7 @@
             *bc = 0;   // (a bid for the same object that reads after this sees 0: flagged as well)
           }
           unsigned long long fm = __ballot(flagged);
-#ifdef MVP_EMD_PROFILE
-          if (lane == 0) atomicAdd(&s_hist2[3], (unsigned long long)__builtin_popcountll(fm) << 32);
-#endif
+          EMD_PROF(if (lane == 0) atomicAdd(&pl.s_hist2[3], (unsigned long long)__builtin_popcountll(fm) << 32);)
           while (fm) {
             const int l = (int)__builtin_ctzll(fm);
             fm &= fm - 1ull;
@@ -141,31 +116,29 @@
             }
           }
         }
-#ifdef MVP_EMD_PROFILE
-        const long long tq1 = __builtin_readcyclecounter();
-        if (contested) atomicAdd(&s_hist2[2], 1ull << 32);
-#endif
+        EMD_PROF(const long long tq1 = __builtin_readcyclecounter();
+                 if (contested) atomicAdd(&pl.s_hist2[2], 1ull << 32);)
         GMT(6)   // [6] contest check
         if (t < Utot) {
           const int m = gm_m;   // the member that placed bid t (it does the stores only one member needs to do)
           if (!contested) {
             if (!last) {
               s_owner[go] = (unsigned short)gj;
-              st_f32(&sc.obj[go].w, gnp);   // (every member: its own next searches read its own store)
+              sa.st_f32(&sc.obj[go].w, gnp);   // (every member: its own next searches read its own store)
               if (prev != 0xFFFF) {
                 // the evicted owner bids again next round: in the list of member (position % W) -- the lists stay
                 // even without any exchange
                 const int d = t % W;
                 const int pos = atomicAdd(&s_gc[gnxt][d], 1);
                 if (d == wg) rec_pos = pos;
-                if (m == wg) st_i32(&ass[prev], -1);
+                if (m == wg) sa.st_i32(&ass[prev], -1);
               }
               s_won[eg & 1u][atomicAdd(&s_nwon[eg & 1u], 1)] = (unsigned short)(go >> lshift);
             }
             if (m == wg) {
-              st_ostate(go, gj);
-              st_i32(&ass[gj], go);
-              if (last) st_f32(&sc.obj[go].w, gnp);
+              sa.st_ostate(go, gj);
+              sa.st_i32(&ass[gj], go);
+              if (last) sa.st_f32(&sc.obj[go].w, gnp);
             }
           } else {
             // lost: stays in its member's list, record carried over through LDS
@@ -187,13 +160,9 @@
         }
         // drain: this member's stores are performed before its next heartbeat says so (and before its own next
         // searches read the prices); the evicted persons' records have arrived
-#ifdef MVP_EMD_PROFILE
-        const long long tq2 = __builtin_readcyclecounter();
-#endif
+        EMD_PROF(const long long tq2 = __builtin_readcyclecounter();)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef MVP_EMD_PROFILE
-        const long long tq3 = __builtin_readcyclecounter();
-#endif
+        EMD_PROF(const long long tq3 = __builtin_readcyclecounter();)
         GMT(8)   // [8] drained
         if (rec_pos >= 0) {
           s_rq[nxt][rec_pos] = pa;
@@ -202,8 +171,6 @@
         lds_barrier();
         GMT(9)   // [9] closing barrier
         if (t == 0) s_cnt[nxt] = s_gc[gnxt][wg];
-#ifdef MVP_EMD_PROFILE
-        tp3 = __builtin_readcyclecounter();
-        if (t == 0) { prof_a1 += tq1 - tq0; prof_a2 += tq2 - tq1; prof_a3 += tq3 - tq2; prof_a4 += tp3 - tq3; prof_an += 1; }
-#endif
+        EMD_PROF(tp3 = __builtin_readcyclecounter();
+                 if (t == 0) { pr.prof_a1 += tq1 - tq0; pr.prof_a2 += tq2 - tq1; pr.prof_a3 += tq3 - tq2; pr.prof_a4 += tp3 - tq3; pr.prof_an += 1; })
       }

@@ -26,13 +26,11 @@
     // bidder inside the band of the object's maximal increment raises the
     // key's bidder field; the increment field stays.
     if (__builtin_expect(any_alarm, 0)) {
-#ifdef MVP_EMD_PROFILE
-      n_alarm += 1;
-#endif
+      EMD_PROF(pr.n_alarm += 1;)
       for (int u = t; u < U; u += kEmdThreads) {
         const int j = s_bj[u], o = s_bo[u];
         const float bi = s_binc[u];
-        const u64 key = ld_key(o);
+        const u64 key = sa.ld_key(o);
         if (emd_in_band(bi, emd_ord2f((unsigned)(key >> 32))))
           atomicMax(reinterpret_cast<u64 *>(&sc.ostate[o]), (key & 0xFFFFFFFF00000000ull) | (u64)((unsigned)j + 1u));
       }
@@ -49,9 +47,7 @@
       s_alarm[(it + 1) & 1] = 0;  // next round's flag; its writers are a barrier away
       s_next = kEmdWaves;         // list positions 0..15 belong to the waves, the rest are drawn
     }
-#ifdef MVP_EMD_PROFILE
-    tp2 = __builtin_readcyclecounter();
-#endif
+    EMD_PROF(tp2 = __builtin_readcyclecounter();)
 
     // ---------------- Assign (emd_cuda.cu:196-215)
     u64 *my_chg = sc.chg + (size_t)wg * kChgCap;
@@ -74,39 +70,33 @@
       if (u >= U) continue;
       const int j = s_bj[u], o = s_bo[u], b2k = s_b2k[u];
       const float bi = s_binc[u];
-#ifdef MVP_EMD_PROFILE
-      const long long ta0 = __builtin_readcyclecounter();
-#endif
-      const int4 os = ld_ostate(o);
-      const float4 oo = ld_obj(o);  // independent of `os`: same round trip
-#ifdef MVP_EMD_PROFILE
-      if (t == 0 && it >= 100) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        prof_a1 += __builtin_readcyclecounter() - ta0;
-        prof_an += 1;
-      }
-#endif
+      EMD_PROF(const long long ta0 = __builtin_readcyclecounter();)
+      const int4 os = sa.ld_ostate(o);
+      const float4 oo = sa.ld_obj(o);  // independent of `os`: same round trip
+      EMD_PROF(if (t == 0 && it >= 100) {
+                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                 pr.prof_a1 += __builtin_readcyclecounter() - ta0;
+                 pr.prof_an += 1;
+               })
       if (last || (unsigned)os.x == (unsigned)j + 1u) {  // a loser may read after the winner reset the key to 0
         const int prev = os.z;
         if (!last && prev != -1) {
           // the evicted owner bids again next round, in this workgroup's list
-          st_i32(&ass[prev], -1);
+          sa.st_i32(&ass[prev], -1);
           const int pos = append();
           if (__builtin_expect(pos >= 0, 1)) {
             {
-              const float4 pa = ld_person(prev, 0);
-              const float4 pb = ld_person(prev, 1);
+              const float4 pa = sa.ld_person(prev, 0);
+              const float4 pb = sa.ld_person(prev, 1);
               s_rq[nxt][pos] = pa;
               s_ri[nxt][pos] = make_int4(prev, __float_as_int(pb.y), __float_as_int(pb.z), 0);
             }
           }
         }
-#ifdef MVP_EMD_PROFILE
-        if (t == 0 && it >= 100) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); prof_a2 += __builtin_readcyclecounter() - ta0; }
-#endif
-        st_ostate(o, j);
-        st_i32(&ass[j], o);
-        st_f32(&sc.obj[o].w, oo.w + bi);
+        EMD_PROF(if (t == 0 && it >= 100) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); pr.prof_a2 += __builtin_readcyclecounter() - ta0; })
+        sa.st_ostate(o, j);
+        sa.st_i32(&ass[j], o);
+        sa.st_f32(&sc.obj[o].w, oo.w + bi);
         // The leaf's price lower bound only changes when the object that just got dearer was (one
         // of) the cheapest of its leaf (the bounds are exact at this point, see the re-scan after
         // the closing barrier): report the leaf; every member of the cluster re-scans the reported
@@ -129,11 +119,7 @@
           s_ri[nxt][pos] = make_int4(j, o, b2k, 0);
         }
       }
-#ifdef MVP_EMD_PROFILE
-      if (t == 0 && it >= 100) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); prof_a3 += __builtin_readcyclecounter() - ta0; }
-#endif
+      EMD_PROF(if (t == 0 && it >= 100) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); pr.prof_a3 += __builtin_readcyclecounter() - ta0; })
     }
-#ifdef MVP_EMD_PROFILE
-    tp3 = __builtin_readcyclecounter();
-    if (t == 0 && it >= 100) prof_a4 += tp3 - tp2;
-#endif
+    EMD_PROF(tp3 = __builtin_readcyclecounter();
+             if (t == 0 && it >= 100) pr.prof_a4 += tp3 - tp2;)

@@ -30,6 +30,7 @@
 // Same rounds, same bids, same bits as every other launch sequence (tests/test_gpu_emd_resident.py).
 #pragma once
 #include "emd_common.h"
+#include "emd_probe.h"
 
 namespace mvp {
 
@@ -70,14 +71,6 @@ __device__ __forceinline__ float row_min(float v) {
   return v;
 }
 
-#ifdef MVP_EMD_PROFILE
-#define RES_PROF_ARGS , long long &prof_seed, long long &prof_subs, long long &prof_folds
-#define RES_PROF_PASS , prof_seed, prof_subs, prof_folds
-#else
-#define RES_PROF_ARGS
-#define RES_PROF_PASS
-#endif
-
 // Bid of one person (emd_cuda.cu:95-179) by the calling wave against the LDS-resident state: the exact best / second-best
 // value and the best slot, wave-uniform.  (qx, qy, qz): the person's point; p1: the slot it last bid on (its 64-slot block
 // is evaluated first); wl: the wave's list of surviving sub-blocks.
@@ -86,9 +79,7 @@ __device__ __forceinline__ BidState res_search(ResShared<NMAX> &sh, unsigned sho
                                                const int p1, const int lane, const int row, const int sl, const int n, const int nsub,
                                                const int npass, const int tpu, const int *__restrict__ perm RES_PROF_ARGS) {
   constexpr int kPasses = NMAX / kResSub / kWave;   // sub-block tests per lane this instantiation can need: 2 / 4
-#ifdef MVP_EMD_PROFILE
-  const long long tb0 = __builtin_readcyclecounter();
-#endif
+  EMD_PROF(const long long tb0 = __builtin_readcyclecounter();)
   const int home = p1 >> 6;   // the 64-slot block (four sub-blocks) that holds the previous best object
   // every sub-block's box and price bound against the bidder's point (independent of the seed: issued first)
   float bd2[kPasses], bpl[kPasses];
@@ -132,9 +123,7 @@ __device__ __forceinline__ BidState res_search(ResShared<NMAX> &sh, unsigned sho
       emd_fold(st, m2, v, home * kWave + lane, n, tpu, perm);   // equal values: the reference's tie order
     }
   }
-#ifdef MVP_EMD_PROFILE
-  prof_seed += __builtin_readcyclecounter() - tb0;
-#endif
+  EMD_PROF(rp.prof_seed += __builtin_readcyclecounter() - tb0;)
   // surviving sub-blocks (the home block's four excluded) compacted into the wave's list
   int nl = 0;
 #pragma unroll
@@ -146,9 +135,7 @@ __device__ __forceinline__ BidState res_search(ResShared<NMAX> &sh, unsigned sho
     if (pass) wl[nl + __builtin_popcountll(m & ((1ull << lane) - 1ull))] = (unsigned short)sub;
     nl += __builtin_popcountll(m);
   }
-#ifdef MVP_EMD_PROFILE
-  prof_subs += nl;
-#endif
+  EMD_PROF(rp.prof_subs += nl;)
   // visit: a step = four sub-blocks, one per 16-lane row; four steps in flight
   for (int k0 = 0; k0 < nl; k0 += 16) {
     // (the list is read past its end -- the row is padded -- and the entry discarded: four independent reads)
@@ -168,9 +155,7 @@ __device__ __forceinline__ BidState res_search(ResShared<NMAX> &sh, unsigned sho
       const float tq = st.tm - o[r].w;
       m[r] = __ballot(slot[r] >= 0 && tq >= 0.f && sd[r] <= tq * tq);
     }
-#ifdef MVP_EMD_PROFILE
-    prof_folds += __builtin_popcountll(m[0]) + __builtin_popcountll(m[1]) + __builtin_popcountll(m[2]) + __builtin_popcountll(m[3]);
-#endif
+    EMD_PROF(rp.prof_folds += __builtin_popcountll(m[0]) + __builtin_popcountll(m[1]) + __builtin_popcountll(m[2]) + __builtin_popcountll(m[3]);)
     // (exact values only for the steps that hold a candidate: 1-2 of the four, usually)
 #pragma unroll
     for (int r = 0; r < 4; ++r)
@@ -276,12 +261,7 @@ __device__ __forceinline__ void emd_resident_body(ResShared<NMAX> &sh, const int
   constexpr bool kSolo = MVP_RES_SOLO != 0 && NMAX <= 2048;
   [[maybe_unused]] int solo_it = -1;   // kSolo: the round from which a single bidder is left (uniform over the workgroup)
   unsigned short *wl = sh.w_list[wave];
-#ifdef MVP_EMD_PROFILE
-  long long prof_folds = 0, prof_subs = 0, prof_bidcyc = 0, prof_nbid = 0, cyc_bid = 0, cyc_sync1 = 0, cyc_assign = 0, prof_slow = 0,
-            prof_seed = 0;
-  const long long t_loop0 = __builtin_readcyclecounter();
-  const long long w_loop0 = wall_clock64();
-#endif
+  EMD_PROF(ResProbe rp;)
   for (int it = it0; it < iters; ++it) {
     const int U = __builtin_amdgcn_readfirstlane(sh.s_act[it % 3]);
     if (U == 0) break;
@@ -318,9 +298,7 @@ __device__ __forceinline__ void emd_resident_body(ResShared<NMAX> &sh, const int
       }
     }
     // ---------------- Bid (emd_cuda.cu:95-179): the wave bids for the persons at its positions, one after the other
-#ifdef MVP_EMD_PROFILE
-    const long long tp0 = __builtin_readcyclecounter();
-#endif
+    EMD_PROF(const long long tp0 = __builtin_readcyclecounter();)
     bool idle = true;
     for (int pos = wave; pos < npos; pos += kEmdWaves) {
       const float4 rq = sh.r_q[pos];
@@ -332,14 +310,10 @@ __device__ __forceinline__ void emd_resident_body(ResShared<NMAX> &sh, const int
       idle = false;
       const float qx = rq.x, qy = rq.y, qz = rq.z;
       const int p1 = __builtin_amdgcn_readfirstlane(sh.r_p1[pos]);
-#ifdef MVP_EMD_PROFILE
-      const long long tb0 = __builtin_readcyclecounter();
-#endif
+      EMD_PROF(const long long tb0 = __builtin_readcyclecounter();)
       BidState st = res_search<NMAX>(sh, wl, qx, qy, qz, p1, lane, row, sl, n, nsub, npass, tpu, sc.perm RES_PROF_PASS);
-#ifdef MVP_EMD_PROFILE
-      prof_bidcyc += __builtin_readcyclecounter() - tb0;
-      prof_nbid += 1;
-#endif
+      EMD_PROF(rp.prof_bidcyc += __builtin_readcyclecounter() - tb0;
+               rp.prof_nbid += 1;)
       if (__builtin_expect(st.bk < 0 || st.b2k < 0, 0)) {   // cannot happen: a block holds 64 objects
         if (lane == 0) sh.s_err = 1;
         st.bk = st.bk < 0 ? 0 : st.bk;
@@ -359,15 +333,11 @@ __device__ __forceinline__ void emd_resident_body(ResShared<NMAX> &sh, const int
       const float pm = row_min(sh.obj[sub * kResSub + sl].w);
       if (sl == 0) sh.s_lo[sub].w = pm;
     }
-#ifdef MVP_EMD_PROFILE
-    const long long tp1 = __builtin_readcyclecounter();
-#endif
+    EMD_PROF(const long long tp1 = __builtin_readcyclecounter();)
     lds_barrier();
-#ifdef MVP_EMD_PROFILE
-    const long long tp2 = __builtin_readcyclecounter();
-    cyc_bid += tp1 - tp0;
-    cyc_sync1 += tp2 - tp1;
-#endif
+    EMD_PROF(const long long tp2 = __builtin_readcyclecounter();
+             rp.cyc_bid += tp1 - tp0;
+             rp.cyc_sync1 += tp2 - tp1;)
     if (last) {
       // every bidder of the last round takes what it bid on (emd_cuda.cu:201-212): resolved below the loop
       last_done = true;
@@ -388,9 +358,7 @@ __device__ __forceinline__ void emd_resident_body(ResShared<NMAX> &sh, const int
       if (__builtin_expect(c != 1, 0)) {
         // another bid in my bucket: compare the round's bids -- the maximal increment bid on my object, then
         // the highest bidder inside its 1e-6 band
-#ifdef MVP_EMD_PROFILE
-        prof_slow += 1;
-#endif
+        EMD_PROF(rp.prof_slow += 1;)
         float mi = inc;
         for (int v = 0; v < npos; ++v)
           if (sh.s_bj[v] >= 0 && sh.s_bo[v] == bk) mi = __builtin_fmaxf(mi, sh.s_binc[v]);
@@ -419,19 +387,9 @@ __device__ __forceinline__ void emd_resident_body(ResShared<NMAX> &sh, const int
       if (lane == 0) sh.s_act[(it + 2) % 3] = 0;
     }
     lds_barrier();
-#ifdef MVP_EMD_PROFILE
-    cyc_assign += __builtin_readcyclecounter() - tp2;
-#endif
+    EMD_PROF(rp.cyc_assign += __builtin_readcyclecounter() - tp2;)
   }
-#ifdef MVP_EMD_PROFILE
-  if (cloud < 2 && lane == 0 && (wave == 0 || wave == 3))
-    printf("resident cloud %d wave %d: rounds %lld bids(all waves) %lld | this wave: %lld bids, %lld cycles each (home block %lld), sub-blocks %.1f folds %.1f per bid | cycles bid %lld wait %lld assign %lld total %lld | contested buckets %lld\n",
-           cloud, wave, n_rounds, n_bids, prof_nbid, prof_bidcyc / (prof_nbid + 1), prof_seed / (prof_nbid + 1), (double)prof_subs / (double)(prof_nbid + 1),
-           (double)prof_folds / (double)(prof_nbid + 1), cyc_bid, cyc_sync1, cyc_assign, __builtin_readcyclecounter() - t_loop0, prof_slow);
-  if (cloud < 2 && lane == 0 && wave == 0)
-    printf("resident cloud %d: %lld cycles in %lld ticks of the 100 MHz clock = %.0f MHz\n", cloud, __builtin_readcyclecounter() - t_loop0,
-           wall_clock64() - w_loop0, 100.0 * (double)(__builtin_readcyclecounter() - t_loop0) / (double)(wall_clock64() - w_loop0));
-#endif
+  EMD_PROF(rp.report(cloud, wave, lane, n_rounds, n_bids);)
 
   // ------------------------------------------------------------ one bidder left: a chain of evictions on ONE wave
   // A single bid is never contested and the person it evicts is the next round's only bidder: the wave that holds the

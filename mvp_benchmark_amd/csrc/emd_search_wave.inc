@@ -4,9 +4,9 @@
 // Names it expects from the including scope:
 //   lane, qx, qy, qz (the bidder's point), hc (its home chunk), p1, p2 (slots of its previous best / second best or -1),
 //   BidState st (b1 = b2 = -1e9, bk = b2k = -1 [, bp]), wl (this wave's list: 4 * kRowListCap unsigned shorts of LDS),
-//   l_lo, l_hi, n_lo, n_hi (the index in LDS), n, nnode, lshift, kch (16-slot chunks per leaf), tpu, sc, ld_obj(slot),
+//   l_lo, l_hi, n_lo, n_hi (the index in LDS), n, nnode, lshift, kch (16-slot chunks per leaf), tpu, sc, sa.ld_obj(slot),
 //   EMD_SEARCH_FOLD(mask, v, slot, price): emd_fold of the including kernel's flavour
-// and, in the profile build, the counters nsub / prof_cells / n_visit / t_visit / prof_fold / prof_more / tb1 / prof_tm_seed.
+// and, in the profile build, EmdBidProbe bp (emd_probe.h); nsub counts the leaves tested.
 // Leaves `linear` (bool: the search scanned every object instead) defined for the statistics.
       const int sub = lane >> 4, sl = lane & 15;
       // (1) Seed: the second-largest exact value among DISTINCT real objects is a lower bound B2 of the final second-best
@@ -18,15 +18,13 @@
         const bool v1 = c1 >= 0, v2 = c2 >= 0 && c2 != c1, v3 = c3 != c1 && c3 != c2, v4 = c4 != c1 && c4 != c2;
         const int cs = sub == 0 ? c1 : sub == 1 ? c2 : sub == 2 ? c3 : c4;
         const bool sv = sub == 0 ? v1 : sub == 1 ? v2 : sub == 2 ? v3 : v4;
-        const float4 o = ld_obj((sv ? cs : 0) * 16 + sl);   // (issued unconditionally: straight-line code up to the reduction)
+        const float4 o = sa.ld_obj((sv ? cs : 0) * 16 + sl);   // (issued unconditionally: straight-line code up to the reduction)
         float v = -__builtin_inff();
         if (sv) v = emd_value(sqdist3(o.x - qx, o.y - qy, o.z - qz), o.w);
         st.tm = (3.0f - emd_wave_second(v)) + kMargin;   // (the home chunk or the chunk that equals it is always there: >= 16 objects)
       }
-#ifdef MVP_EMD_PROFILE
-      tb1 = __builtin_readcyclecounter();
-      prof_tm_seed = st.tm;
-#endif
+      EMD_PROF(bp.tb1 = __builtin_readcyclecounter();
+               bp.prof_tm_seed = st.tm;)
       // (2) the nodes: one lane each, one step
       unsigned long long nmask = __ballot(emd_box_pass(n_lo[lane], n_hi[lane], qx, qy, qz, st.tm));
       // When the whole cloud is within reach (high prices everywhere, e.g. a clustered prediction against a spread
@@ -39,10 +37,8 @@
       // (4) visit the listed leaves, 4 * kVisitLoads per step: each 16-lane row takes kVisitLoads leaves, so that many independent 16-byte loads per
       // lane are in flight at once and a typical bid (~6-10 surviving leaves) needs ONE dependent memory round trip here.
       auto visit = [&]() {
-#ifdef MVP_EMD_PROFILE
-        const long long tv0 = __builtin_readcyclecounter();
-        n_visit += (nlist + 4 * kVisitLoads - 1) / (4 * kVisitLoads);
-#endif
+        EMD_PROF(const long long tv0 = __builtin_readcyclecounter();
+                 bp.n_visit += (nlist + 4 * kVisitLoads - 1) / (4 * kVisitLoads);)
         for (int k0 = 0; k0 < nlist; k0 += 4 * kVisitLoads) {
           // (straight-line: the list entries are read unconditionally -- entries behind the list's end are
           // clamped and discarded -- so that they share ONE LDS round trip)
@@ -58,24 +54,20 @@
             float4 o[kVisitLoads];
 #pragma unroll
             for (int r = 0; r < kVisitLoads; ++r)
-              o[r] = in[r] ? ld_obj(s[r] + 16 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
+              o[r] = in[r] ? sa.ld_obj(s[r] + 16 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
             for (int r = 0; r < kVisitLoads; ++r) {
               const float sd = sqdist3(o[r].x - qx, o[r].y - qy, o[r].z - qz);
               const float tq = st.tm - o[r].w;
               const bool ps = in[r] && tq >= 0.f && sd <= tq * tq;
               const unsigned long long m = __ballot(ps);
-#ifdef MVP_EMD_PROFILE
-              prof_fold += __builtin_popcountll(m);
-#endif
+              EMD_PROF(bp.prof_fold += __builtin_popcountll(m);)
               if (m) EMD_SEARCH_FOLD(m, emd_value(sd, o[r].w), s[r] + 16 * c, o[r].w);
             }
           }
         }
         nlist = 0;
-#ifdef MVP_EMD_PROFILE
-        t_visit += __builtin_readcyclecounter() - tv0;
-#endif
+        EMD_PROF(bp.t_visit += __builtin_readcyclecounter() - tv0;)
       };
       // (3) the leaves of the passing nodes, four nodes per step (a 16-lane row each)
       while (nmask) {
@@ -96,17 +88,15 @@
         all_near = false;
         if (lpass) wl[nlist + __builtin_popcountll(lm & ((1ull << lane) - 1ull))] = (unsigned short)leaf;
         nlist += __builtin_popcountll(lm);
-#ifdef MVP_EMD_PROFILE
-        nsub += 64;
-        prof_cells += __builtin_popcountll(lm);
-#endif
+        EMD_PROF(nsub += 64;
+                 bp.prof_cells += __builtin_popcountll(lm);)
         if (nlist > 4 * kRowListCap - kWave) visit();   // keep room for the next step's 64 leaves
       }
       if (__builtin_expect(linear, 0)) {
         for (int base = 0; base < n; base += 4 * kWave) {
           float4 o[4];
 #pragma unroll
-          for (int r = 0; r < 4; ++r) o[r] = ld_obj(base + r * kWave + lane);  // n % 1024 == 0
+          for (int r = 0; r < 4; ++r) o[r] = sa.ld_obj(base + r * kWave + lane);  // n % 1024 == 0
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const float sd = sqdist3(o[r].x - qx, o[r].y - qy, o[r].z - qz);
