@@ -267,10 +267,20 @@ int mvp_knn_sorted(int b, int n, int m, int nsample, const float *xyz,
  * reference: completion/model_utils.py:242-247 builds `-xx - inner - xx^T` on a
  * materialised (B,N,N) matrix and calls torch.topk).  dot (b,n,n) = x^T x from a
  * library GEMM, sq (b,n) = |x_i|^2 -> idx (b,n,k): per row i the k largest of
- * fl(fl(-sq[j] + 2 dot[i][j]) - sq[i]), sorted descending (self first); equal
- * to torch.topk's indices wherever the values are distinct.  k <= n; k <= 64 and
- * n <= 16384: one wave per row streaming the matrix (equal values keep the lower
- * column first); otherwise the tile kernel, k <= 47 (MVP_EBADSHAPE beyond). */
+ * val[i][j] = fl(fl(-sq[j] - fl(-2 dot[i][j])) - sq[i]), sorted descending (self
+ * first); equal to torch.topk's indices wherever the values are distinct.  k <= n.
+ *  - k <= 64 and n <= 16384 (one wave per row streaming the matrix): exactly the
+ *    top k by (value descending, column ascending) -- among equal values the lower
+ *    columns are chosen and come first, at the cut too, and -0 == +0.  The result
+ *    does not depend on n % 4 or on the alignment of `dot` (which only pick the
+ *    load width).  Columns whose value is NaN or -inf are never chosen: a row
+ *    with fewer than k others lists those first, in order, and fills the rest of
+ *    its slots with column 0, so every index is in [0, n).
+ *  - otherwise (n > 16384) the tile kernel, k <= 47 (MVP_EBADSHAPE beyond): the k
+ *    largest values in descending order at k distinct columns (NaN and -inf as
+ *    above); which of several columns of equal value is taken, and their order,
+ *    is unspecified, so the indices are pinned only where a value differs from
+ *    its neighbours. */
 int mvp_topk_gram(int b, int n, int k, const float *dot, const float *sq,
                   int *idx, void *stream);
 

@@ -520,8 +520,9 @@ __global__ __launch_bounds__(kFkRows) void topk_gram_kernel(
 // is inserted with a one-lane shift (DPP wave_shr) of the entries behind it.
 // After the first few hundred columns a row admits a candidate every ~35
 // columns (k ln(n/k) insertions in total), so the kernel is a stream of the
-// 4 n^2 bytes.  The list is ordered by (key, column): equal keys keep the lower
-// column first whatever the visiting order.
+// 4 n^2 bytes.  The list is ordered by (key, column) and the screen admits by the
+// same order, so the result is the top k by (value, lower column) whatever the
+// visiting order (VEC = 4 visits columns 0,4,8,.. then 1,5,9,.. of a segment).
 constexpr int kTwWaves = 4;   // waves (= rows in flight) per workgroup
 constexpr int kTwRows = 8;    // consecutive rows per wave
 
@@ -542,7 +543,9 @@ __global__ __launch_bounds__(kTwWaves * kWave) void topk_gram_wave_kernel(
     const float sqi = s_sq[row];
     float lv = __builtin_inff();  // key = -value, ascending in lanes 0..k-1; lanes >= k never shift
     int li = 0;  // slots never filled (fewer than k finite keys: NaN input) point at column 0
-    float tau = __builtin_inff();  // exclusive bound: a candidate must be strictly smaller
+    float tau = __builtin_inff();  // a candidate above it is never wanted; one equal to it only as a tie (below)
+    float tk = __builtin_inff();   // the list's last entry (key, column), wave-uniform: a candidate with the same
+    int ti = 0;                    // key and a lower column replaces it (list not full: +inf, nothing ties)
     // Until k entries are in, the list's k-th key is +inf and everything would
     // pass the screen.  The first block of columns gives a bound for free: the
     // largest of the 64 per-lane minima has >= 64 >= k keys at or below it.
@@ -555,13 +558,16 @@ __global__ __launch_bounds__(kTwWaves * kWave) void topk_gram_wave_kernel(
       const bool pgt = __builtin_amdgcn_update_dpp(0, gt ? 1 : 0, 0x138, 0xF, 0xF, true) != 0;
       lv = gt ? (pgt ? plv : kv) : lv;
       li = gt ? (pgt ? pli : col) : li;
-      tau = __builtin_fminf(seed, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lv), k - 1)));
+      tk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lv), k - 1));
+      ti = __builtin_amdgcn_readlane(li, k - 1);
+      tau = __builtin_fminf(seed, tk);
     };
     // seed = the k-th smallest of the 64 per-lane minima of the first block (k
     // keys at or below it): radix select on the order-preserving bit pattern,
     // one ballot per bit, all bookkeeping scalar.
     auto seed_from = [&](float lane_min) {
-      const unsigned fb = __float_as_uint(lane_min);
+      // a lane that saw only NaN keys counts as +inf (a NaN's bit pattern would rank by its sign bit)
+      const unsigned fb = __float_as_uint(lane_min == lane_min ? lane_min : __builtin_inff());
       const unsigned ord = (fb & 0x80000000u) ? ~fb : (fb | 0x80000000u);
       unsigned long long cand = ~0ull;
       unsigned prefix = 0u;
@@ -586,12 +592,16 @@ __global__ __launch_bounds__(kTwWaves * kWave) void topk_gram_wave_kernel(
       tau = seed;
     };
     auto screen = [&](float key, int colbase, int colstride) {  // lane's candidate: column colbase + colstride * lane
-      unsigned long long m = __ballot(key < tau);
+      if (__ballot(key <= tau) == 0ull) return;  // the stream: one compare per 64 candidates
+      // rare from here on.  Wanted: below the bound, or level with the list's last entry at a lower column
+      // (seed is exclusive and above every list entry, so key == seed never passes)
+      unsigned long long m = __ballot(key < tau || (key == tk && colbase + colstride * lane < ti));
       while (m) {
         const int l = __builtin_ctzll(m);
         m &= m - 1ull;
         const float kv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(key), l));
-        if (kv < tau) insert(kv, colbase + colstride * l);  // wave-uniform
+        const int col = colbase + colstride * l;
+        if (kv < tau || (kv == tk && col < ti)) insert(kv, col);  // wave-uniform; tau, tk, ti move with every insert
       }
     };
     if constexpr (VEC == 4) {  // n % 4 == 0: rows are 16-byte aligned

@@ -352,8 +352,10 @@ def gram_topk(dot, sq, k):
     """Feature-space neighbours: dot (B,N,N) = x^T x, sq (B,N) = |x_i|^2 ->
     idx (B,N,k) int32, per row the k largest of (-sq[j] + 2 dot[i][j]) - sq[i]
     in descending order (self first) -- the selection model_utils.knn makes with
-    torch.topk on the materialised negative-distance matrix, in one scan.  Not
-    part of the reference's operator set (row N1 of the widening plan)."""
+    torch.topk on the materialised negative-distance matrix, in one scan.  Equal
+    values: the lower column, whatever dot's alignment (k <= 64, N <= 16384;
+    larger N: unspecified -- include/mvpops.h).  Not part of the reference's
+    operator set (row N1 of the widening plan)."""
     _need_contiguous(dot, sq)
     B, N = sq.shape
     idx = _new(dot, B, N, k, dtype=torch.int32)

@@ -47,7 +47,7 @@ def test_calc_cd_and_calc_emd_formulas(oracle):
     np.testing.assert_allclose(e.cpu().numpy(), np.sqrt(od).mean(1), rtol=1e-6)
 
 
-def test_coordinate_knn_goes_through_the_op(oracle):
+def test_coordinate_knn_goes_through_the_op(oracle, monkeypatch):
     """model_utils.knn / knn_point_idx on coordinates use the
     fused knn operator.  Pinned three ways: (1) bit-identical to the oracle's
     knn (the operator's own contract), (2) the chosen neighbours are the true k
@@ -73,11 +73,19 @@ def test_coordinate_knn_goes_through_the_op(oracle):
     gap = np.abs(np.take_along_axis(d2, ref_idx, -1) - chosen)
     assert (gap[differ] < 2e-6).all() and differ.mean() < 1e-3
     # feature-space searches: library GEMM + one scan of the Gram matrix; the
-    # same indices as topk on the materialised matrix wherever values differ
+    # same indices as topk on the materialised matrix wherever values differ.
+    # (8, 130, 70): k > 64 is beyond the operator, mu.knn takes its PyTorch
+    # formulation there (exact selection, ties and the tile kernel of n > 16384:
+    # tests/test_gpu_gram_topk.py)
+    op_calls = []
+    gram_topk = mu.gram_topk
+    monkeypatch.setattr(mu, "gram_topk", lambda dot, sq, k: op_calls.append(k) or gram_topk(dot, sq, k))
     for C, n, kk in [(24, 700, 16), (48, 1024, 16), (256, 300, 4), (5, 40, 40), (24, 3072, 20), (8, 130, 64),
                      (8, 130, 70), (16, 257, 1)]:
         feat = dev(rand_clouds(7 + C, 2, C, n))
+        del op_calls[:]
         got = mu.knn(feat, kk)
+        assert op_calls == ([kk] if kk <= 64 else [])            # the operator, except for the fallback case
         assert got.shape == (2, n, kk) and got.dtype == torch.int64
         sq = (feat * feat).sum(dim=1, keepdim=True)
         neg = -sq - (-2 * torch.matmul(feat.transpose(2, 1), feat)) - sq.transpose(2, 1)
