@@ -58,7 +58,15 @@ const char *mvp_last_hip_error(void);
  * (chamfer3D.cu:12-134).
  * xyz1 (b,n,3), xyz2 (b,m,3) -> dist1 (b,n), idx1 (b,n): squared distance to
  * and index of the nearest point of xyz2; dist2/idx2 (b,m): roles swapped.
- * Ties: lowest index wins.  Outputs are fully overwritten (n,m >= 1). */
+ * Ties: lowest index wins.  Outputs are fully overwritten (n,m >= 1).
+ * Non-finite input (this entry point and mvp_chamfer_forward_sorted, bit for
+ * bit the same): a candidate whose computed distance is NaN is never the
+ * nearest.  +inf is a value like any other (lowest index among the candidates
+ * at the minimum).  A query for which every distance is NaN gets dist = NaN
+ * (quiet, positive: 0x7fc00000) and idx = 0.  Every index is in [0, m)
+ * whatever the input.  The reference agrees on a NaN query; for a NaN
+ * *candidate* its result depends on the candidate's place in a 512-tile and is
+ * not reproduced. */
 int mvp_chamfer_forward(int b, int n, int m, const float *xyz1,
                         const float *xyz2, float *dist1, float *dist2,
                         int *idx1, int *idx2, void *stream);
@@ -239,7 +247,9 @@ int mvp_furthest_point_sampling_cluster(int b, int n, int m, int w, const float 
  * ball_query_kernel_launcher (src/ball_query_cuda.cu:56-78).
  * new_xyz (b,m,3) centres, xyz (b,n,3) -> idx (b,m,nsample).  Rows with no
  * hit keep the zeros the caller put there (ball_query.py:35); this
- * implementation writes every slot itself, so idx need not be pre-zeroed. */
+ * implementation writes every slot itself, so idx need not be pre-zeroed.
+ * Non-finite input: a distance that is NaN is no hit, so a centre with a NaN
+ * coordinate gets a row of zeros and points with a NaN coordinate are skipped. */
 int mvp_ball_query(int b, int n, int m, float min_radius, float max_radius,
                    int nsample, const float *new_xyz, const float *xyz,
                    int *idx, void *stream);
@@ -248,7 +258,11 @@ int mvp_ball_query(int b, int n, int m, float min_radius, float max_radius,
  * -> knn_kernel_launcher (src/knn_cuda.cu:97-115).
  * xyz (b,n,3), new_xyz (b,m,3) -> idx (b,m,nsample), dist2 (b,m,nsample),
  * ascending; 1 <= nsample <= 100.  Slot order follows the reference's
- * max-heap + heap-sort (knn_cuda.cu:26-53). */
+ * max-heap + heap-sort (knn_cuda.cu:26-53).
+ * As in the reference the heap starts at (1e10, 0) and admits by strict `<`:
+ * a distance that is NaN, +inf or >= 1e10 is never admitted, and a query with
+ * fewer than nsample admissible candidates keeps (1e10, 0) in the slots left
+ * (last, the list being ascending).  Every index is in [0, n). */
 int mvp_knn(int b, int n, int m, int nsample, const float *xyz,
             const float *new_xyz, int *idx, float *dist2, void *stream);
 
@@ -257,7 +271,8 @@ int mvp_knn(int b, int n, int m, int nsample, const float *xyz,
  * irrelevant) and every query searches outwards through boxed tiles, keeping k + 1 candidates; queries
  * whose k + 1 smallest distances are not pairwise different (lattices, duplicates: there the reference's
  * result depends on its sequence of heap operations, knn_cuda.cu:26-53,80-90) are recomputed by the
- * exhaustive kernel.  n < 4096, m < 1024 or nsample > 32: forwards to mvp_knn. */
+ * exhaustive kernel.  n < 4096, m < 1024 or nsample > 32: forwards to mvp_knn.  Non-finite input: equal to
+ * mvp_knn on the same input (such queries end with equal 1e10 slots and take the recomputation). */
 long long mvp_knn_scratch_bytes(int b, int n, int m);
 int mvp_knn_sorted(int b, int n, int m, int nsample, const float *xyz,
                    const float *new_xyz, int *idx, float *dist2, void *scratch,
@@ -287,7 +302,10 @@ int mvp_topk_gram(int b, int n, int k, const float *dot, const float *sq,
 /* Replaces interpolate_ext.three_nn_wrapper
  * (utils/mm3d_pn2/ops/interpolate/src/interpolate.cpp:46-56,88) ->
  * three_nn_kernel_launcher (src/three_nn_cuda.cu:67-89).
- * unknown (b,n,3), known (b,m,3) -> dist2 (b,n,3) SQUARED, idx (b,n,3). */
+ * unknown (b,n,3), known (b,m,3) -> dist2 (b,n,3) SQUARED, idx (b,n,3).
+ * The three bests start at (+inf, 0) and are replaced by strict `<`: a distance
+ * that is NaN or +inf is never selected, and with fewer than three others the
+ * slots left keep (+inf, 0). */
 int mvp_three_nn(int b, int n, int m, const float *unknown,
                  const float *known, float *dist2, int *idx, void *stream);
 

@@ -26,6 +26,10 @@ namespace mvp {
 constexpr int kCdThreads = 256;
 constexpr int kCdTile = 1024;  // candidates per LDS tile (12 KiB)
 constexpr int kCdSub = 16;     // candidates per min-tracking sub-tile
+// Distance written for a query whose distances are ALL NaN (index 0 with it):
+// the quiet, positive NaN, whatever payload the arithmetic produced.
+constexpr unsigned kCdNanBits = 0x7fc00000u;
+constexpr unsigned kCdInfBits = 0x7f800000u;
 
 template <int Q>
 __global__ __launch_bounds__(kCdThreads) void nm_distance_kernel(
@@ -118,7 +122,26 @@ __global__ __launch_bounds__(kCdThreads) void nm_distance_kernel(
         found = true;
       }
     }
-    result[j] = best[q];
+    float bd = best[q];
+    if (bd == __builtin_inff()) {
+      // No finite distance (overflowing squares, non-finite coordinates): fminf
+      // dropped every NaN and no sub-tile ever lowered `best`, so `bsub` says
+      // nothing.  +inf is a value like any other -- the first candidate at +inf
+      // wins -- and a query whose distances are all NaN gets (NaN, 0).  Rare and
+      // per lane, hence a plain scan of the query's candidates.
+      bd = __uint_as_float(kCdNanBits);
+      bi = 0;
+      for (int k = 0; k < m; ++k) {
+        const float d = sqdist3(cpts[k * 3 + 0] - qx[q], cpts[k * 3 + 1] - qy[q],
+                                cpts[k * 3 + 2] - qz[q]);
+        if (d == __builtin_inff()) {
+          bd = d;
+          bi = k;
+          break;
+        }
+      }
+    }
+    result[j] = bd;
     result_i[j] = bi;
   }
 }
@@ -208,9 +231,11 @@ __global__ __launch_bounds__(kCsThreads) void chamfer_sort_kernel(
   if (!(ext > 0.f) || !(ext < 3.0e38f)) ext = 1.f;
   const float invh = 16.f / ext;
   auto cell_of = [&](float x, float y, float z) {
-    const int ix = min(15, max(0, (int)((x - lo[0]) * invh)));
-    const int iy = min(15, max(0, (int)((y - lo[1]) * invh)));
-    const int iz = min(15, max(0, (int)((z - lo[2]) * invh)));
+    // clamped as floats: 0 * inf (a subnormal extent makes invh = +inf), a NaN
+    // or an infinite coordinate must not reach the float -> int conversion
+    const int ix = (int)__builtin_fminf(__builtin_fmaxf((x - lo[0]) * invh, 0.f), 15.f);
+    const int iy = (int)__builtin_fminf(__builtin_fmaxf((y - lo[1]) * invh, 0.f), 15.f);
+    const int iz = (int)__builtin_fminf(__builtin_fmaxf((z - lo[2]) * invh, 0.f), 15.f);
     return cs_spread4(ix) | (cs_spread4(iy) << 1) | (cs_spread4(iz) << 2);
   };
   for (int k = t; k < cnt; k += kCsThreads)
@@ -395,8 +420,19 @@ __global__ __launch_bounds__(kCdThreads) void nm_distance_sorted_kernel(
 #pragma unroll
   for (int q = 0; q < Q; ++q) {
     if (qorig[q] >= 0) {
-      result[qorig[q]] = __uint_as_float((unsigned)(best[q] >> 32));
-      result_i[qorig[q]] = (int)(unsigned)best[q];
+      // NaN bits sort above +inf, so a NaN key is the minimum only when every
+      // distance of the query is NaN; a padding entry (+inf coordinates) is the
+      // minimum only when every real candidate's distance is: both are the
+      // "all NaN" query of the contract, written as (NaN, 0) like the
+      // exhaustive kernel does.
+      unsigned dbits = (unsigned)(best[q] >> 32);
+      int bi = (int)(unsigned)best[q];
+      if (dbits > kCdInfBits || bi == kCsPad) {
+        dbits = kCdNanBits;
+        bi = 0;
+      }
+      result[qorig[q]] = __uint_as_float(dbits);
+      result_i[qorig[q]] = bi;
     }
   }
 }

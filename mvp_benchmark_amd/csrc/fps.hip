@@ -427,9 +427,10 @@ __global__ __launch_bounds__(1024) void fps_sort_kernel(int n, int npad, const f
     return v;
   };
   auto cell_of = [&](float x, float y, float z) {
-    const int ix = min(15, max(0, (int)((x - lo[0]) * invh)));
-    const int iy = min(15, max(0, (int)((y - lo[1]) * invh)));
-    const int iz = min(15, max(0, (int)((z - lo[2]) * invh)));
+    // clamped as floats: 0 * inf (a subnormal extent makes invh = +inf) must not reach the float -> int conversion
+    const int ix = (int)__builtin_fminf(__builtin_fmaxf((x - lo[0]) * invh, 0.f), 15.f);
+    const int iy = (int)__builtin_fminf(__builtin_fmaxf((y - lo[1]) * invh, 0.f), 15.f);
+    const int iz = (int)__builtin_fminf(__builtin_fmaxf((z - lo[2]) * invh, 0.f), 15.f);
     return spread4(ix) | (spread4(iy) << 1) | (spread4(iz) << 2);
   };
   for (int k = t; k < n; k += 1024) atomicAdd(&s_cnt[cell_of(in[k * 3 + 0], in[k * 3 + 1], in[k * 3 + 2])], 1);
