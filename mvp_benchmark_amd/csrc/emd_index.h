@@ -241,12 +241,25 @@ __device__ __forceinline__ void emd_node_price(const float4 *l_lo, float4 *n_lo,
 
 // The conservative box test of a search (emd_common.h: kMargin): can the box {lo.xyz .. hi.xyz} with price bound lo.w
 // hold an object whose value reaches the running second best?  tm = fl(fl(3 - B2) + kMargin).  Empty box: false.
-__device__ __forceinline__ bool emd_box_pass(const float4 lo, const float4 hi, float qx, float qy, float qz, float tm) {
+// The two halves of the test: the squared distance to the box needs only the box and the point, the comparison only that
+// distance, the box's price bound and the threshold.
+__device__ __forceinline__ float emd_box_dist2(const float4 lo, const float4 hi, float qx, float qy, float qz) {
   const float dx = __builtin_fmaxf(__builtin_fmaxf(lo.x - qx, qx - hi.x), 0.f);
   const float dy = __builtin_fmaxf(__builtin_fmaxf(lo.y - qy, qy - hi.y), 0.f);
   const float dz = __builtin_fmaxf(__builtin_fmaxf(lo.z - qz, qz - hi.z), 0.f);
+  return sqdist3(dx, dy, dz);
+}
+__device__ __forceinline__ bool emd_box_reach(float d2, float pm, float tm) {
+  const float tq = tm - pm;
+  return (tq >= 0.f) & (d2 <= tq * tq);
+}
+// FLAT: both conditions are evaluated unconditionally, so that a box read from LDS is ONE read (with `&&` the compiler
+// reads the price bound, waits, and reads the corners behind a branch: two dependent LDS round trips per test).
+template <bool FLAT = false>
+__device__ __forceinline__ bool emd_box_pass(const float4 lo, const float4 hi, float qx, float qy, float qz, float tm) {
+  if constexpr (FLAT) return emd_box_reach(emd_box_dist2(lo, hi, qx, qy, qz), lo.w, tm);
   const float tq = tm - lo.w;
-  return tq >= 0.f && sqdist3(dx, dy, dz) <= tq * tq;
+  return tq >= 0.f && emd_box_dist2(lo, hi, qx, qy, qz) <= tq * tq;
 }
 
 }  // namespace mvp

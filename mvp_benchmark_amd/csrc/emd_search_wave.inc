@@ -9,24 +9,33 @@
 // and, in the profile build, EmdBidProbe bp (emd_probe.h); nsub counts the leaves tested.
 // Leaves `linear` (bool: the search scanned every object instead) defined for the statistics.
       const int sub = lane >> 4, sl = lane & 15;
+      float nd2, npm;   // this lane's node: squared distance of the point to its box, its price bound (read in (1), tested in (2))
       // (1) Seed: the second-largest exact value among DISTINCT real objects is a lower bound B2 of the final second-best
       // value.  Four chunks of 16 slots, one per 16-lane row, in ONE memory round trip: the chunks of the previous best
       // and second-best objects (after a lost contest or an eviction the next best is usually one of their neighbours),
       // the bidder's home chunk and its sibling.  Duplicates are dropped (an object must not count twice).
       {
-        const int c1 = p1 >= 0 ? p1 >> 4 : -1, c2 = p2 >= 0 ? p2 >> 4 : -1, c3 = hc, c4 = hc ^ 1;
-        const bool v1 = c1 >= 0, v2 = c2 >= 0 && c2 != c1, v3 = c3 != c1 && c3 != c2, v4 = c4 != c1 && c4 != c2;
-        const int cs = sub == 0 ? c1 : sub == 1 ? c2 : sub == 2 ? c3 : c4;
-        const bool sv = sub == 0 ? v1 : sub == 1 ? v2 : sub == 2 ? v3 : v4;
+        // (the row's chunk and its validity from the bits of `sub`, all selects: a chain of `sub == r ? :` becomes a
+        // switch, which is lowered to a tree of divergent branches -- 8 exec regions in front of the load)
+        const int c1 = max(p1, -1) >> 4, c2 = max(p2, -1) >> 4;   // (-1 >> 4 == -1: no previous object)
+        const int odd = sub & 1;
+        const bool hi = sub >= 2;   // rows 2, 3: the home chunk hc and its sibling hc ^ 1
+        const int cs = hi ? hc ^ odd : (odd ? c2 : c1);
+        const bool sv = (hi | (cs >= 0)) & ((sub == 0) | (cs != c1)) & ((sub < 2) | (cs != c2));
         const float4 o = sa.ld_obj((sv ? cs : 0) * 16 + sl);   // (issued unconditionally: straight-line code up to the reduction)
-        float v = -__builtin_inff();
-        if (sv) v = emd_value(sqdist3(o.x - qx, o.y - qy, o.z - qz), o.w);
+        // (under the load's round trip: the part of the node test (2) that does not need the threshold)
+        const float4 nlo = n_lo[lane], nhi = n_hi[lane];
+        nd2 = emd_box_dist2(nlo, nhi, qx, qy, qz);
+        npm = nlo.w;
+        // (a row without a chunk of its own has loaded chunk 0: valued like the others -- no branch -- and dropped)
+        const float val = emd_value(sqdist3(o.x - qx, o.y - qy, o.z - qz), o.w);
+        const float v = sv ? val : -__builtin_inff();
         st.tm = (3.0f - emd_wave_second(v)) + kMargin;   // (the home chunk or the chunk that equals it is always there: >= 16 objects)
       }
       EMD_PROF(bp.tb1 = __builtin_readcyclecounter();
                bp.prof_tm_seed = st.tm;)
       // (2) the nodes: one lane each, one step
-      unsigned long long nmask = __ballot(emd_box_pass(n_lo[lane], n_hi[lane], qx, qy, qz, st.tm));
+      unsigned long long nmask = __ballot(emd_box_reach(nd2, npm, st.tm));
       // When the whole cloud is within reach (high prices everywhere, e.g. a clustered prediction against a spread
       // target) the boxes only add overhead: every node passes AND so do all 64 leaves of the first step -> scan the
       // objects linearly, 4 x 64 per step, with the same lossless filter.  (Decided on the leaves, not on the nodes:
@@ -46,7 +55,7 @@
           bool in[kVisitLoads];
 #pragma unroll
           for (int r = 0; r < kVisitLoads; ++r) {
-            const int cw = wl[min(k0 + r * 4 + sub, 4 * kRowListCap - 1)];
+            const int cw = wl[min(k0 + r * 4 + sub, nlist - 1)];   // (behind the list's end: its last leaf again, loaded like the others and discarded)
             in[r] = k0 + r * 4 + sub < nlist;
             s[r] = (cw << lshift) + sl;
           }
@@ -54,7 +63,7 @@
             float4 o[kVisitLoads];
 #pragma unroll
             for (int r = 0; r < kVisitLoads; ++r)
-              o[r] = in[r] ? sa.ld_obj(s[r] + 16 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
+              o[r] = sa.ld_obj(s[r] + 16 * c);
 #pragma unroll
             for (int r = 0; r < kVisitLoads; ++r) {
               const float sd = sqdist3(o[r].x - qx, o[r].y - qy, o[r].z - qz);
@@ -71,15 +80,17 @@
       };
       // (3) the leaves of the passing nodes, four nodes per step (a 16-lane row each)
       while (nmask) {
-        int nd[4];
+        // the next four nodes as the bytes of one scalar (a node is a lane: < 64; 0xFF = none), a row takes its byte
+        unsigned nd4 = 0u;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          nd[r] = nmask ? (int)__builtin_ctzll(nmask) : -1;
+          nd4 |= (nmask ? (unsigned)__builtin_ctzll(nmask) : 0xFFu) << (8 * r);
           nmask &= nmask - 1ull;
         }
-        const int node = sub == 0 ? nd[0] : sub == 1 ? nd[1] : sub == 2 ? nd[2] : nd[3];
+        const unsigned nb = (nd4 >> (8 * sub)) & 0xFFu;
+        const int node = nb == 0xFFu ? -1 : (int)nb;
         const int leaf = max(node, 0) * kNodeFan + sl;
-        const bool lpass = node >= 0 && emd_box_pass(l_lo[leaf], l_hi[leaf], qx, qy, qz, st.tm);
+        const bool lpass = (node >= 0) & emd_box_pass<true>(l_lo[leaf], l_hi[leaf], qx, qy, qz, st.tm);
         const unsigned long long lm = __ballot(lpass);
         if (__builtin_expect(all_near && lm == ~0ull, 0)) {
           linear = true;
