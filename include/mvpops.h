@@ -473,12 +473,16 @@ int mvp_share_gather_sum_grad(int b, int share, int cw, int k, int n_src, int n,
  *         its rows ldw floats apart (0 = dense; a (cout, cin) weight with cin % 4 != 0
  *         is read with 16-byte loads when the caller pads its rows to ldw % 4 == 0)
  *   xmask (b, cin, len) or NULL: x is taken as 0 where xmask <= 0 (the data
- *         gradient of a fused ReLU: x = grad_out, xmask = the layer's output)
+ *         gradient of a fused ReLU: x = grad_out, xmask = the layer's output);
+ *         aten.threshold_backward's select -- an Inf of x is dropped there, not
+ *         multiplied, and x passes where xmask is NaN
  *   t[b,co,l] = sum_ci w(co,ci) x[b,ci,l] + bias[co]        (bias may be NULL)
- *   t = max(t, 0)                                           if relu
+ *   t = t < 0 ? 0 : t  (torch.relu: a NaN stays a NaN)      if relu
  *   u[b,co,g] = max_{l in group g} t[b,co,l]                groups of `group`
  *                                                            consecutive columns
- *                                                            (1, 2, 4, ..., 32)
+ *                                                            (1, 2, 4, ..., 32);
+ *                                                            NaN if a member is
+ *                                                            (torch.max)
  *   y[b,co,g] = u + residual[b,co,g]                        (residual may be NULL)
  * y, residual: (b, cout, len / group).  len % 4 == 0, len % group == 0, x 16-byte
  * aligned.  The data gradient of the plain map is the same call with the forward
@@ -494,17 +498,21 @@ int mvp_pointwise_mfma(int b, int cin, int cout, int len, const float *x,
  * pre-activation ReLUs of SA_module; :151,172 and :255-296 residual sums followed by ReLU; :283-285 conv6 over
  * cat(global feature tiled, features); :160,172 conv1 / conv_res of one input).  mvp_pointwise_mfma is this call
  * with bias_per_cloud = 0, flags = relu ? MVP_PW_RELU : 0, m_split = 0.
- *   flags  MVP_PW_X_RELU       x counts as max(x, 0) (on load; x itself is not written)
- *          MVP_PW_RELU         t = max(t, 0) before the group maximum and the residual (mvp_pointwise_mfma's relu)
- *          MVP_PW_RES_IS_MASK  `residual` is a mask: y = residual > 0 ? u : 0 instead of u + residual -- the data
- *                              gradient of conv(relu(x)): W^T grad_out where x > 0
- *          MVP_PW_RELU_AFTER   y = max(y, 0) after the residual / mask
+ *   flags  MVP_PW_X_RELU       x counts as relu(x) (on load; x itself is not written)
+ *          MVP_PW_RELU         t = relu(t) before the group maximum and the residual (mvp_pointwise_mfma's relu)
+ *          MVP_PW_RES_IS_MASK  `residual` is a mask: y = residual <= 0 ? 0 : u instead of u + residual -- the data
+ *                              gradient of conv(relu(x)): aten.threshold_backward(W^T grad_out, x, 0)
+ *          MVP_PW_RELU_AFTER   y = relu(y) after the residual / mask
+ *          Non-finite values: relu(t) is the select t < 0 ? 0 : t, so a NaN stays a NaN as under torch.relu (never
+ *          fmaxf, which would answer 0); the masks (xmask, gymask, RES_IS_MASK) are threshold_backward's select, so u
+ *          passes where the mask is NaN and an Inf of u is dropped where the mask is <= 0; the group maximum is NaN if a
+ *          member is (torch.max).  These are what autograd of the float32 PyTorch composition yields on every route.
  *   bias_per_cloud != 0: bias is (b, cout) -- the share of a per-cloud vector in a convolution over
  *          cat(vector tiled over the positions, features) -- instead of (cout)
  *   m_split (0, or a multiple of 32 below cout; then residual == NULL, group == 1, y2 != NULL): output rows below
  *          m_split go to y (b, m_split, len), the others to y2 (b, cout - m_split, len).
  * Arithmetic: the same k-ordered fmaf chain per output as mvp_pointwise_mfma; every fused step is the exact
- * float operation the separate pass would perform (max, add, select). */
+ * float operation the separate pass would perform (add, select), non-finite inputs included. */
 #define MVP_PW_RELU 1
 #define MVP_PW_RELU_AFTER 2
 #define MVP_PW_RES_IS_MASK 4
@@ -520,7 +528,8 @@ int mvp_pointwise_mfma_ex(int b, int cin, int cout, int len, const float *x,
  * (completion/models/pcn.py:29-30; vrcnet.py:281-282 conv5; ecg.py:137-138 gf_conv) -- without writing the
  * (b, cout, len) tensor: val (b, cout) = the maxima, idx (b, cout) int32 = the first position that attains each
  * (what torch.max reports; the sparse backward pass mvp_pointwise_max_backward takes it).  Arithmetic as
- * mvp_pointwise_mfma: val equals its output reduced with max, bit for bit.  keys: b * cout * 8 bytes of caller
+ * mvp_pointwise_mfma: val equals its output reduced with max, bit for bit; a NaN in a row (of either sign, with or without
+ * the ReLU) makes val NaN and idx the first NaN, as torch.max reports.  keys: b * cout * 8 bytes of caller
  * scratch, 8-byte aligned, contents irrelevant.  w (cout, cin) row-major with row stride ldw (0 = cin). */
 int mvp_pointwise_mfma_max(int b, int cin, int cout, int len, const float *x, const float *w, int ldw,
                            const float *bias, int relu, float *val, int *idx, void *keys, long long keys_bytes,
@@ -528,7 +537,8 @@ int mvp_pointwise_mfma_max(int b, int cin, int cout, int len, const float *x, co
 
 /* Weight (and bias) gradient of the same map on the matrix cores:
  *   gw[co,ci] = sum_b sum_l g[b,co,l] x[b,ci,l],  gb[co] = sum_b sum_l g[b,co,l]
- * with g = gy, or gy where gymask > 0 and 0 elsewhere (fused ReLU).  gb may be
+ * with g = gy, or 0 where gymask <= 0 and gy elsewhere (fused ReLU: aten.threshold_backward's
+ * select, so gy passes where gymask is NaN).  gb may be
  * NULL.  The b*len positions are split over workgroups that write partial
  * tiles into `scratch` (mvp_pointwise_wgrad_mfma_scratch_bytes(...) bytes; 0 =
  * shape not covered), a second kernel adds them in a fixed order: no float
@@ -540,7 +550,7 @@ int mvp_pointwise_wgrad_mfma(int b, int cin, int cout, int len, const float *x,
                              const float *gy, const float *gymask, float *gw,
                              float *gb, void *scratch, long long scratch_bytes,
                              void *stream);
-/* ABI 18.  x_relu != 0: x counts as max(x, 0) on load -- the weight gradient of conv(relu(x)) from the
+/* ABI 18.  x_relu != 0: x counts as relu(x) (NaN stays NaN) on load -- the weight gradient of conv(relu(x)) from the
  * tensor the layer was handed, not from a stored relu(x). */
 int mvp_pointwise_wgrad_mfma_ex(int b, int cin, int cout, int len, const float *x, int x_relu,
                                 const float *gy, const float *gymask, float *gw,

@@ -40,6 +40,38 @@ constexpr int kMmThreads = 256;
 constexpr int kXC = 0, kKC = 1;    // operand images (above)
 constexpr int kImgPad = 4;         // floats; keeps rows 16-byte aligned and shifts their banks
 
+// Non-finite contract of every fused step = what the float32 PyTorch pass it replaces yields:
+//   ReLU (prologue and every epilogue): torch.relu -- a NaN stays a NaN.  A select, not fmaxf: fmaxf(NaN, 0) is 0, which
+//     turned a diverged layer into clean zeros on this route only.
+//   ReLU' (xmask / gymask on load, the residual as a mask): aten.threshold_backward(v, mask, 0) -- 0 where mask <= 0, v
+//     elsewhere, so a NaN in the mask lets v through (what autograd of torch.relu does) and an Inf in v is dropped, not
+//     multiplied by 0.
+//   the group maximum and the row maximum: torch.max -- a NaN member makes the result NaN.
+// Cost: a select is v_cmp + v_cndmask where fmaxf was one v_max_f32, on every stored element of the epilogue.  Registers and
+// occupancy of all 12 forward / data-gradient instances are unchanged (88-144 VGPRs, 3-5 waves per SIMD as before; two
+// SGPRs fewer).  Measured against the parent's kernels, both libraries in one process, alternating, 7 rounds x 20 calls,
+// median ms, in brackets the parent's own min..max (B x (Cin -> Cout) x L):
+//   forward + ReLU          64 x (128 -> 256) x 2048   0.1032 [0.0989..0.1140] -> 0.1059    64 x (512 -> 512) x 2048  0.6058 [0.6026..0.6076] -> 0.6034
+//                           64 x (512 -> 1024) x 2048  1.1845 [1.1838..1.1863] -> 1.1835    64 x (64 -> 64) x 3072    0.0261 [0.0251..0.0339] -> 0.0278
+//                           64 x (128 -> 128) x 1536   0.0387 [0.0380..0.0389] -> 0.0390 *  32 x (128 -> 256) x 16384 0.3611 [0.3562..0.3896] -> 0.3617
+//   ReLU, + residual, ReLU  64 x (128 -> 256) x 2048   0.1587 [0.1577..0.1624] -> 0.1592    64 x (64 -> 64) x 3072    0.0389 [0.0387..0.0393] -> 0.0398 *
+//                           64 x (64 -> 128) x 3072    0.0701 [0.0695..0.0706] -> 0.0706 *  32 x (128 -> 256) x 16384 0.5284 [0.5276..0.5361] -> 0.5374 *
+//   data gradient, xmask    64 x (128 -> 256) x 2048   0.0902 [0.0891..0.0924] -> 0.0916    64 x (64 -> 64) x 3072    0.0291 [0.0287..0.0293] -> 0.0298 *
+//   weight gradient, gymask 64 x (128 -> 256) x 2048   0.1179 [0.1166..0.1187] -> 0.1178    64 x (512 -> 512) x 2048  0.7118 [0.7108..0.7128] -> 0.7124
+//   row maximum + ReLU      64 x (512 -> 1024) x 2048  1.2090 [1.2075..1.2097] -> 1.2147 *
+//   group maximum + ReLU    not measured for the formulation that ships (fmaxf + fix-up, see the group epilogue below); the
+//                           one it replaced: 32 x (64 -> 128) x 1024 groups of 32  0.4612 [0.4592..0.4623] -> 0.5091
+// (*) outside the parent's spread: calls of 25-70 us by 1-2.3 %, the 0.53 ms residual call by 1.7 %, the row maximum by
+// 0.5 %.  Also outside, not listed above: the plain forward 64 x (128 -> 256) x 2048 0.0992 [0.0987..0.0996] -> 0.1004,
+// data gradient with xmask 64 x (64 -> 128) x 3072 0.0450 [0.0446..0.0454] -> 0.0456, with xmask and the input mask
+// 64 x (64 -> 64) x 3072 0.0446 [0.0439..0.0447] -> 0.0451.  That is 9 of the 42 group-1 shape x epilogue pairs measured
+// (11 forward shapes; plain, residual, both data gradients and the weight gradient at six of them; the row maximum); the
+// other 33 are inside the parent's spread or faster.  Whole models (bench.py, 20 steps, parent | change alternating,
+// three runs each): VRCNet training step 18.39 / 18.42 / 18.45 -> 18.41 / 18.40 / 18.50 ms, PCN evaluation step 22.56 /
+// 22.49 / 22.47 -> 22.52 / 22.51 / 22.47 ms.
+__device__ __forceinline__ float pw_relu(float v) { return v < 0.f ? 0.f : v; }
+__device__ __forceinline__ float pw_masked(float v, float mask) { return mask <= 0.f ? 0.f : v; }
+
 template <int BX, int BK, int MODE>
 struct PwImg {
   static constexpr int ld = (MODE == kXC ? BX : BK) + kImgPad;
@@ -107,7 +139,7 @@ __device__ __forceinline__ void pw_fetch(PwRegs<BX * BK / 4 / kMmThreads> &r,
   }
 }
 
-// registers -> LDS image (16-byte stores); with MASK, a value counts as 0 where its mask is <= 0; with SELF_RELU
+// registers -> LDS image (16-byte stores); with MASK, a value counts as 0 where its mask is <= 0 (pw_masked); with SELF_RELU
 // (round 6; a template parameter: as a run-time flag it cost the forward kernel 16 %) where it is < 0 itself: the operand is relu(.) of what lies in memory -- a pre-activation
 // ReLU (vrcnet.py:34,54: conv(relu(x))) costs no pass over x and no second tensor
 template <int BX, int BK, int MODE, bool MASK, bool SELF_RELU = false>
@@ -118,17 +150,17 @@ __device__ __forceinline__ void pw_stash(float *img, const PwRegs<BX * BK / 4 / 
   for (int i = 0; i < V; ++i) {
     const int q = t + i * kMmThreads;
     float4 v = r.v[i];
-    if constexpr (SELF_RELU) {                 // (a select, not fmaxf: a NaN stays a NaN, as torch.relu leaves it)
-      v.x = v.x < 0.f ? 0.f : v.x;
-      v.y = v.y < 0.f ? 0.f : v.y;
-      v.z = v.z < 0.f ? 0.f : v.z;
-      v.w = v.w < 0.f ? 0.f : v.w;
+    if constexpr (SELF_RELU) {
+      v.x = pw_relu(v.x);
+      v.y = pw_relu(v.y);
+      v.z = pw_relu(v.z);
+      v.w = pw_relu(v.w);
     }
     if constexpr (MASK) {
-      v.x = rm.v[i].x > 0.f ? v.x : 0.f;
-      v.y = rm.v[i].y > 0.f ? v.y : 0.f;
-      v.z = rm.v[i].z > 0.f ? v.z : 0.f;
-      v.w = rm.v[i].w > 0.f ? v.w : 0.f;
+      v.x = pw_masked(v.x, rm.v[i].x);
+      v.y = pw_masked(v.y, rm.v[i].y);
+      v.z = pw_masked(v.z, rm.v[i].z);
+      v.w = pw_masked(v.w, rm.v[i].w);
     }
     if constexpr (MODE == kXC) {
       const int k = q / (BX / 4), x = (q % (BX / 4)) * 4;
@@ -298,7 +330,7 @@ __global__ __launch_bounds__(kMmThreads) __attribute__((amdgpu_waves_per_eu(TM =
         for (int j = 0; j < TN; ++j) {
           const int col = n0 + wn * 32 * TN + j * 32 + lrow;
           float v = acc[i][j][r] + bi;
-          if (relu) v = __builtin_fmaxf(v, 0.f);
+          if (relu) v = pw_relu(v);
           // order-preserving key, > 0; -0 counts as +0 (the first position of a tie wins, as torch.max reports) and a NaN
           // of either sign takes the top key (torch.max propagates NaN; unpacked as a NaN again)
           const unsigned b = __float_as_uint(v + 0.f);
@@ -342,7 +374,7 @@ __global__ __launch_bounds__(kMmThreads) __attribute__((amdgpu_waves_per_eu(TM =
           for (int r = 0; r < 16; ++r) {
             const int dr = (r & 3) + 8 * (r >> 2);
             float v = acc[i][j][r] + bv[r];
-            v = relu_any ? __builtin_fmaxf(v, 0.f) : v;
+            v = relu_any ? pw_relu(v) : v;
             if (dr < rows_left) yc[(size_t)dr * N] = v;
           }
         }
@@ -384,9 +416,9 @@ __global__ __launch_bounds__(kMmThreads) __attribute__((amdgpu_waves_per_eu(TM =
           for (int r = 0; r < 16; ++r) {
             const int dr = (r & 3) + 8 * (r >> 2);
             float v = acc[i][j][r] + bv[r];
-            v = relu ? __builtin_fmaxf(v, 0.f) : v;
-            if (rbse) v = res_is_mask ? (rv[r] > 0.f ? v : 0.f) : v + rv[r];
-            v = relu_after ? __builtin_fmaxf(v, 0.f) : v;
+            v = relu ? pw_relu(v) : v;
+            if (rbse) v = res_is_mask ? pw_masked(v, rv[r]) : v + rv[r];
+            v = relu_after ? pw_relu(v) : v;
             if (dr < rows_left) yb[o0 + (size_t)dr * N] = v;
           }
         }
@@ -405,16 +437,22 @@ __global__ __launch_bounds__(kMmThreads) __attribute__((amdgpu_waves_per_eu(TM =
         const int lr = wm * 32 * TM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
         const int row = m0 + lr;
         float v = acc[i][j][r] + sbias[lr];
-        if (relu) v = __builtin_fmaxf(v, 0.f);
+        if (relu) v = pw_relu(v);
         if (col >= N) v = -__builtin_inff();              // (N % group == 0: a group is inside or outside)
+        // torch.max: a NaN member makes the group's maximum NaN.  fmaxf drops a NaN, so the members' NaN bits are taken
+        // first (one compare per value, its wave-wide result a scalar) and the maximum is fixed up after the reduction,
+        // behind a wave-uniform branch no finite tile takes.  (NaN-aware selects in every step of the reduction measured
+        // 8-10 % on the whole kernel: 0.461 -> 0.509 ms at 32 x (64 -> 128) x 1024 groups of 32.)
+        const unsigned long long nan_lanes = __ballot(v != v);
         for (int off = 1; off < group; off <<= 1) v = __builtin_fmaxf(v, __shfl_xor(v, off, 64));
+        if (nan_lanes != 0ull && ((nan_lanes >> (lane & ~(group - 1))) & ((1ull << group) - 1ull)) != 0ull) v = __builtin_nanf("");
         if (row < M && col < N && (lrow & (group - 1)) == 0) {
           const size_t o = (size_t)row * len_out + col / group;
           if (rbse) {
             const float rv = rbse[o];
-            v = res_is_mask ? (rv > 0.f ? v : 0.f) : v + rv;
+            v = res_is_mask ? pw_masked(v, rv) : v + rv;
           }
-          if (relu_after) v = __builtin_fmaxf(v, 0.f);
+          if (relu_after) v = pw_relu(v);
           yb[o] = v;
         }
       }

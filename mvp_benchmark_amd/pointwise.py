@@ -106,11 +106,13 @@ PW_RELU, PW_RELU_AFTER, PW_RES_IS_MASK, PW_X_RELU = 1, 2, 4, 8     # include/mvp
 def mfma_linear(x, w2d, bias=None, relu=False, residual=None, group=1, w_kmajor=False, xmask=None, x_relu=False,
                 relu_after=False, res_is_mask=False, bias_per_cloud=False, m_split=0):
     """y = epilogue(W x) for x (B, Cin, ...) contiguous float32 CUDA, W = w2d (Cout, Cin) -- or its
-    transpose (Cin, Cout) with w_kmajor; with xmask, x counts as 0 where xmask <= 0; with x_relu where it is
-    <= 0 itself.  Epilogue (mvp_pointwise_mfma_ex): + bias (one per cloud with bias_per_cloud: (B, Cout)), ReLU,
+    transpose (Cin, Cout) with w_kmajor; with xmask, x counts as 0 where xmask <= 0 (aten.threshold_backward's select:
+    x passes where xmask is NaN, an Inf of x is dropped, not multiplied); with x_relu, x counts as relu(x) (a NaN stays
+    a NaN).  Epilogue (mvp_pointwise_mfma_ex): + bias (one per cloud with bias_per_cloud: (B, Cout)), ReLU,
     max over groups of `group` consecutive positions of the flattened trailing dimensions, + residual (or, with
-    res_is_mask, zero where residual <= 0), ReLU again with relu_after.  m_split > 0: two outputs, the rows below
-    m_split and the others -> (y, y2).  No autograd."""
+    res_is_mask, zero where residual <= 0 and unchanged elsewhere, also where residual is NaN), ReLU again with
+    relu_after.  Every ReLU keeps a NaN like torch.relu, the group maximum is NaN if a member is (torch.max).
+    m_split > 0: two outputs, the rows below m_split and the others -> (y, y2).  No autograd."""
     B = x.size(0)
     cin = x.size(1)
     cout = w2d.size(1) if w_kmajor else w2d.size(0)
@@ -138,7 +140,8 @@ def mfma_linear(x, w2d, bias=None, relu=False, residual=None, group=1, w_kmajor=
 
 def mfma_wgrad(x, gy, cout, cin, with_bias, gymask=None, x_relu=False):
     """(gw (Cout, Cin), gb (Cout) | None) of y = W x + b from x (B, Cin, ...) and gy (B, Cout, ...);
-    with gymask, gy counts as 0 where gymask <= 0; with x_relu, x as 0 where it is <= 0 (mvp_pointwise_wgrad_mfma_ex)."""
+    with gymask, gy counts as 0 where gymask <= 0 (aten.threshold_backward's select: gy passes where gymask is NaN); with
+    x_relu, x counts as relu(x), a NaN staying a NaN (mvp_pointwise_wgrad_mfma_ex)."""
     B = x.size(0)
     length = x[0, 0].numel()
     nbytes = pointwise_wgrad_mfma_scratch_bytes(B, cin, cout, length, with_bias)
@@ -211,10 +214,11 @@ class _PointwiseConv(Function):
             and x.size(0) * x[0, 0].numel() >= MFMA_WGRAD_MIN_POSITIONS \
             and pointwise_wgrad_mfma_scratch_bytes(x.size(0), cin, cout, x[0, 0].numel(), ctx.has_bias) > 0
         # ReLU'(.): the MFMA kernels mask grad_out by the saved output on load; the other routes get
-        # the masked tensor
+        # the masked tensor.  Every route takes threshold_backward's convention (0 where y <= 0, grad_out elsewhere -- what
+        # autograd of torch.relu does): never a multiply, which would turn an Inf of grad_out at y <= 0 into NaN
         mask = y if ctx.relu else None
         if ctx.relu and ((need_x and not gx_mfma) or ((need_w or need_b) and not gw_mfma)):
-            gy_masked = gy * (y > 0)
+            gy_masked = torch.ops.aten.threshold_backward(gy, y, 0)
         else:
             gy_masked = gy
         gx = gw = gb = None
@@ -301,7 +305,8 @@ class _PointwiseConvFused(Function):
     if relu_after, in ONE GEMM (mvp_pointwise_mfma_ex): the pre-activation ReLUs, residual sums and per-cloud vectors of the
     relational encoder (vrcnet.py:34-57, 151, 172, 283-296) cost no elementwise pass forward.  Backward: ONE pass masks
     grad_out by the output where a residual or a per-cloud bias needs the masked tensor itself (otherwise the GEMMs mask on
-    load), the data gradient masks its output by x > 0 in its epilogue, the weight gradient takes relu(x) on load."""
+    load), the data gradient zeroes its output where x <= 0 in its epilogue (threshold_backward's convention like every
+    ReLU' here: it passes where x is NaN), the weight gradient takes relu(x) on load."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, cloud_bias, residual, relu_in, relu, relu_after):
