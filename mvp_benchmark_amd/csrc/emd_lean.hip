@@ -223,13 +223,19 @@ __device__ __forceinline__ int emd_lean_body(LeanShared &sh, const int cloud, co
   const bool gm_ok = WB != 1 && n <= kGMaxN && (fast_ok & 2) != 0;   // (fast_ok: bit 0 = same-XCD stores, bit 1 = gathered-bid rounds)
   unsigned eg = (unsigned)resume->epoch_g;
   int goff = 0, gi = 0;
+  int gU = 0;   // this member's bidders of the coming gathered-bid round (with goff: derived where the lists are counted)
+  // The events of a round's end -- this launch's last round, the auction's last round, hand-over to the resident
+  // kernel, collapse to member 0, everybody assigned -- happen in a handful of a launch's rounds: the launch constants
+  // behind them are folded into one round threshold and one person threshold, and the round's path holds one test of
+  // `it + 1` and `Utot` against them (emd_lean_round_end.inc; the predicates themselves sit behind it, unchanged).
+  constexpr int kLeanSoloMax = kFewMax > kSoloMax ? kFewMax : kSoloMax;   // persons at which the cluster collapses to member 0
+  const int it_cold = min(it_stop, iters), u_cold = max(u_stop, kLeanSoloMax);
   EMD_GMTIME(long long gmt[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; long long gm_prev = 0;)   // phase clock (emd_probe.h: GMT)
   // The rounds of at most 16 bidders (emd_lean_round_few.inc) take a collapsed cluster's cloud when the leaves hold 16 slots
   // (n <= 16384 = the owner map's size) and this launch runs to the auction's end; a resident hand-over below 16 persons
   // -- a test knob -- keeps the plain rounds (they watch for it).  (A lambda, evaluated where it is needed: two more
   // scalars alive through the round loops cost the gathered-bid rounds 900 more SGPR spill moves.)
   auto few_ok = [&]() { return MVP_EMD_FEW != 0 && n <= kGMaxN && lshift == 4 && it_stop >= iters && (u_stop <= 0 || u_stop >= kFewMax); };
-  constexpr int kLeanSoloMax = kFewMax > kSoloMax ? kFewMax : kSoloMax;   // persons at which the cluster collapses to member 0
   int stop_cnt = -1;   // >= 0: the loop ended before round it + 1 with this many entries in this member's next list
   bool stop_for_res = false;   // ... because at most u_stop persons are left (not because round it_stop is next)
   EMD_PROF(EmdProbe pr;)
@@ -243,6 +249,16 @@ __device__ __forceinline__ int emd_lean_body(LeanShared &sh, const int cloud, co
   auto rounds = [&](auto gm_tag) -> int {
   constexpr bool GM = decltype(gm_tag)::value;
   constexpr bool gm = GM;
+  if constexpr (GM) {
+    // this member's bidders and its first position in the cloud-wide order of bids, for the first of these rounds; the
+    // end of every round derives the next round's from the counts it reads anyway
+    const int cv = s_gc[gi][lane & (kMaxCluster - 1)];   // (one LDS read; the sum is scalar work)
+    goff = 0;
+#pragma unroll
+    for (int w = 0; w + 1 < WM; ++w)
+      if (w < wg) goff += __builtin_amdgcn_readlane(cv, w);
+    gU = __builtin_amdgcn_readlane(cv, wg);
+  }
   for (; it < iters; ++it) {
     int sw = 0;   // 2: gathered-bid rounds from the next round on; 3: back to the plain rounds (member 0 alone)
     if (Utot == 0) break;
@@ -250,27 +266,20 @@ __device__ __forceinline__ int emd_lean_body(LeanShared &sh, const int cloud, co
     // gathered-bid round: every member's list length (scalar registers), this member's first position in the
     // cloud-wide order, and the heartbeat -- "every store this member issued in earlier rounds is performed" (the
     // previous settle ended with a drain); the others' settle of THIS round waits for it
-    const int gcur = gi, gnxt = gi == 2 ? 0 : gi + 1, gzero = gi == 0 ? 2 : gi - 1;   // (rotating: this round's lengths, the next round's, the set cleared meanwhile)
+    const int gnxt = gi == 2 ? 0 : gi + 1, gzero = gi == 0 ? 2 : gi - 1;   // (rotating; s_gc[gi]: this round's lengths -- in gU, goff by now --, the next round's, the set cleared meanwhile)
     if constexpr (WB != 1) {
       if constexpr (GM) {
         ++eg;
         EMD_GMTIME(if (gm_prev) GMT(0) else gm_prev = __builtin_readcyclecounter();)   // [0] end of the last round's bookkeeping -> this round's start
         EMD_GMTIME(gmt[15] += 1; GMT(14) GMT(14))   // [14] = two stamps back to back (calibration)
-        goff = 0;
-        {
-          const int cv = s_gc[gcur][lane & (kMaxCluster - 1)];   // (one LDS read; the sum is scalar work)
-#pragma unroll
-          for (int w = 0; w + 1 < WM; ++w)
-            if (w < wg) goff += __builtin_amdgcn_readlane(cv, w);
-        }
-        if (t == 0 && s_gc[gcur][wg] == 0) {   // (a member with bidders: its last bid of the round raises the word)
+        if (t == 0 && gU == 0) {   // (a member with bidders: its last bid of the round raises the word)
           u64 *hb = bid_area + (size_t)(eg & 1u) * kGStride + 2 * kGCap + wg;
           if (same_xcd) __hip_atomic_store(hb, (u64)eg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
           else __hip_atomic_store(hb, (u64)eg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
       }
     }
-    const int U = gm ? s_gc[gcur][wg] : s_cnt[cur];  // this workgroup's bidders
+    const int U = gm ? gU : s_cnt[cur];  // this workgroup's bidders
     n_rounds += 1;
     n_bids += U;
     const bool last = it == iters - 1;

@@ -1,7 +1,7 @@
 // Part of emd_lean_body's round loop (csrc/emd_lean.hip), included INSIDE the loop body: end of a round -- next list sizes, hand-over / stop checks, collapse to member 0, rebalance, refreshed price bounds, entry into the gathered-bid rounds.
 // every name used here is a local of emd_lean_body / of the `rounds` lambda (GM = gathered-bid rounds).
     // ---------------- end of round: next list sizes + refreshed price bounds
-    if (clustered) {
+    if (GM || clustered) {   // (the gathered-bid rounds are a cluster's: the round that collapses it leaves them)
       EMD_PROF(long long tpd = tp3, tpg2 = tp3;)
       Utot = 0;
       bool overflow = false;
@@ -33,54 +33,68 @@
             chgw[w] = 0;
             Utot += cntw[w];
           }
+          // the next round's bidders of this member and its first position in the cloud-wide order (this round's are
+          // no longer needed); the length of the next list for the rounds that follow a collapse to member 0
+          goff = 0;
+#pragma unroll
+          for (int w = 0; w + 1 < WM; ++w)
+            if (w < wg) goff += cntw[w];
+          gU = __builtin_amdgcn_readlane(cv, wg);
+          if (t == 0) s_cnt[nxt] = gU;
         }
-        // the rounds end here (last round, or everybody assigned): what follows reads the other members' stores
-        if (it + 1 >= iters || Utot == 0) {
+      }
+      // (one test for all the events of a round's end: it_cold, u_cold in emd_lean.hip)
+      if (__builtin_expect(it + 1 >= it_cold || Utot <= u_cold, 0)) {
+        if constexpr (GM) {
+          // the rounds end here (last round, or everybody assigned): what follows reads the other members' stores
+          if (it + 1 >= iters || Utot == 0) {
+            if (!emd_cluster_gather_n<WM>(slots, W, wg, ++epoch, &s_nchg, &s_nchg, s_gout, &s_abort, same_xcd)) {
+              aborted = true;
+              break;
+            }
+          }
+        }
+        if (__builtin_expect((it + 1 == it_stop && it + 1 < iters && Utot > 0) ||
+                             (Utot <= u_stop && Utot > 0 && iters - (it + 1) >= kResMinRounds), 0)) {
+          // ---- this launch's last round: the lists are left for the next launch below the loop
+          stop_cnt = cntw[wg];
+          stop_for_res = !(it + 1 == it_stop);
+          break;
+        }
+        if (__builtin_expect(Utot > 0 && Utot <= kLeanSoloMax && it + 1 < iters, 0)) {
+          // ---- hand everything to member 0 (lists of <= kSoloMax persons live
+          // in LDS only: publish the person ids; their records are in memory)
+          if (wg != 0 && t < cntw[wg]) sa.st_i32(my_ulist + t, s_ri[nxt][t].x);
           if (!emd_cluster_gather_n<WM>(slots, W, wg, ++epoch, &s_nchg, &s_nchg, s_gout, &s_abort, same_xcd)) {
             aborted = true;
             break;
           }
-        }
-      }
-      if (__builtin_expect((it + 1 == it_stop && it + 1 < iters && Utot > 0) ||
-                           (Utot <= u_stop && Utot > 0 && iters - (it + 1) >= kResMinRounds), 0)) {
-        // ---- this launch's last round: the lists are left for the next launch below the loop
-        stop_cnt = cntw[wg];
-        stop_for_res = !(it + 1 == it_stop);
-        break;
-      }
-      if (__builtin_expect(Utot > 0 && Utot <= kLeanSoloMax && it + 1 < iters, 0)) {
-        // ---- hand everything to member 0 (lists of <= kSoloMax persons live
-        // in LDS only: publish the person ids; their records are in memory)
-        if (wg != 0 && t < cntw[wg]) sa.st_i32(my_ulist + t, s_ri[nxt][t].x);
-        if (!emd_cluster_gather_n<WM>(slots, W, wg, ++epoch, &s_nchg, &s_nchg, s_gout, &s_abort, same_xcd)) {
-          aborted = true;
-          break;
-        }
-        if (wg != 0) {
-          if (t == 0) atomicAdd(reinterpret_cast<unsigned long long *>(&stats[1]), (unsigned long long)n_bids);
-          ret_early = true;
-          return 0;
-        }
-        int idx = t;
-#pragma unroll
-        for (int w = 1; w < WM; ++w) {
-          if (idx >= 0 && idx < cntw[w]) {
-            const int jj = __hip_atomic_load(sc.ulist + (size_t)w * 2 * n + idx, __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_AGENT);
-            const float4 pa = sa.ld_person(jj, 0);
-            const float4 pb = sa.ld_person(jj, 1);
-            const int pos = atomicAdd(&s_cnt[nxt], 1);
-            s_rq[nxt][pos] = pa;
-            s_ri[nxt][pos] = make_int4(jj, __float_as_int(pb.y), __float_as_int(pb.z), 0);
+          if (wg != 0) {
+            if (t == 0) atomicAdd(reinterpret_cast<unsigned long long *>(&stats[1]), (unsigned long long)n_bids);
+            ret_early = true;
+            return 0;
           }
-          idx -= cntw[w];
+          int idx = t;
+#pragma unroll
+          for (int w = 1; w < WM; ++w) {
+            if (idx >= 0 && idx < cntw[w]) {
+              const int jj = __hip_atomic_load(sc.ulist + (size_t)w * 2 * n + idx, __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_AGENT);
+              const float4 pa = sa.ld_person(jj, 0);
+              const float4 pb = sa.ld_person(jj, 1);
+              const int pos = atomicAdd(&s_cnt[nxt], 1);
+              s_rq[nxt][pos] = pa;
+              s_ri[nxt][pos] = make_int4(jj, __float_as_int(pb.y), __float_as_int(pb.z), 0);
+            }
+            idx -= cntw[w];
+          }
+          clustered = false;
+          if constexpr (GM) sw = 3;
+          if (t == 0) s_nchg = 0;
+          __syncthreads();
         }
-        clustered = false;
-        if constexpr (GM) sw = 3;
-        if (t == 0) s_nchg = 0;
-        __syncthreads();
-      } else {
+      }
+      if (!GM && clustered) {
         // ---- rebalance: the round lasts as long as the fullest workgroup's
         // bid passes (16 bidders per pass, 64 in row mode).  When an even
         // split would need fewer passes than the fullest list does, lists

@@ -170,7 +170,6 @@
         }
         lds_barrier();
         GMT(9)   // [9] closing barrier
-        if (t == 0) s_cnt[nxt] = s_gc[gnxt][wg];
         EMD_PROF(tp3 = __builtin_readcyclecounter();
                  if (t == 0) { pr.prof_a1 += tq1 - tq0; pr.prof_a2 += tq2 - tq1; pr.prof_a3 += tq3 - tq2; pr.prof_a4 += tp3 - tq3; pr.prof_an += 1; })
       }
