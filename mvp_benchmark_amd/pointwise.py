@@ -3,18 +3,46 @@ networks.  Same parameters and state_dict layout as nn.Conv1d /
 nn.Conv2d(kernel_size=1); the reference builds these layers with nn.Conv1d /
 nn.Conv2d directly (completion/models/pcn.py, ecg.py, vrcnet.py).
 
-Routing on float32 CUDA tensors (include/mvpops.h), training and inference alike:
-  * layers with >= 32 input and output channels: all three passes on the float32
-    MFMA GEMMs of csrc/pointwise_mfma.hip -- forward `mvp_pointwise_mfma` with bias /
-    ReLU / residual / max-over-neighbours fused into its epilogue, data gradient
-    the same kernel on the transposed weight with ReLU' applied to grad_out on
-    load, weight + bias gradient `mvp_pointwise_wgrad_mfma` (ReLU' on load, the
-    NCHW operands read as they lie: no layout transposes);
-  * layers with <= 64 x 64 channels: weight gradient `mvp_pointwise_wgrad`, data
-    gradient `mvp_pointwise_dgrad` (one pass over gy, weights from LDS);
-  * everything else (and every non-CUDA / non-float32 tensor): the library
-    convolution.
+Routing.  Every entry point describes its layer (`_describe` -> `Layer`: device, dtype, shape, layout of x and the
+weight -- no tensors) and a pure planner turns the description, what needs a gradient and the route selectors below into
+named routes; the autograd Functions branch on the names.  "ours" = float32 CUDA, 3-d / 4-d, positions L > 0 a multiple
+of 4, at most 65535 clouds; "small" = ours with <= 64 x 64 channels; "mfma" = ours, USE_MFMA, >= MFMA_MIN_CH channels, x
+and the weight dense and 16-byte aligned; "fits" = _gemm_fits.
+
+  pass                 route     rule                                                                    runs
+  pointwise_conv       function  a gradient is wanted and: dense and (mfma or small) and (MFMA_TRAIN or  _PointwiseConv
+    (_plan_conv)                 small) -- or USE_MFMA, float32 CUDA, x not empty (any layout: the
+                                 backward pass below never calls the library's backward-data kernels)
+                       autograd  a gradient is wanted otherwise                                          conv1d / conv2d
+                       none      no gradient wanted                                                      the forward alone
+    forward            mfma      mfma and fits(cout x cin) and (cout >= 32 or cin <=                     mvp_pointwise_mfma_ex
+                                 MFMA_SKINNY_FWD_MAX_CIN); under `function` also MFMA_TRAIN or small,
+                                 on the contiguous copies; under `none` only from dense tensors
+                       library   otherwise                                                               _library_conv
+  data gradient        small     small                                                                   mvp_pointwise_dgrad
+    (_plan_conv_       mfma      MFMA_DGRAD, mfma but for x's layout, cin % 4 == 0, fits(cin x cout)     mvp_pointwise_mfma_ex (W^T)
+     backward)         gemm      otherwise                                                               torch.matmul
+  weight gradient      mfma      mfma, not small, cin >= MFMA_WGRAD_MIN_CIN, B * L >=                    mvp_pointwise_wgrad_mfma_ex
+                                 MFMA_WGRAD_MIN_POSITIONS, the kernel's scratch query > 0
+                       small     small, x 16-byte aligned (the kernel refuses a view at an odd offset)   mvp_pointwise_wgrad
+                       gemm      LIBRARY_IS_GEMM or L % 4 != 0                                           torch.einsum
+                       miopen    otherwise                                                               aten.convolution_backward
+    premask                      ReLU and a wanted gradient whose route is not mfma (those mask on load) aten.threshold_backward
+  pointwise_conv_fused fused     dense, mfma, fits forward, (x needs a gradient: cin % 4 == 0 and fits   one GEMM
+    (_plan_fused)                the data gradient), the weight-gradient conditions (also for
+                                 inference), float32 residual / cloud_bias, not relu with a residual
+                       composed  otherwise                                                               pointwise_conv + elementwise
+  pointwise_conv_dual  stacked   cout1 % 32 == 0, both layers `fused`, the stacked forward `mfma`        one GEMM, two outputs
+    (_plan_dual)       separate  otherwise                                                               two pointwise_conv
+  pointwise_conv_max   function  a gradient is wanted and: not CUDA, or the sparse kernel's shapes       _PointwiseConvMax
+    (_plan_max)        autograd  a gradient is wanted otherwise                                          pointwise_conv, max
+    forward            fused     float32 CUDA, not empty, dense weight, forward `mfma`                   mvp_pointwise_mfma_max
+                       conv_max  otherwise                                                               pointwise_conv, max
+    backward           sparse    the kernel's shapes ((3 cout + L) * 4 <= 30000), x and weight dense     mvp_pointwise_max_backward
+     (_plan_max_backward) torch  otherwise (host tensors, other dtypes)                                  scatter_add_ / gather
 """
+from collections import namedtuple
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -22,6 +50,8 @@ from torch.autograd import Function
 
 from ._lib import call, pointwise_max_backward_scratch_bytes, pointwise_wgrad_mfma_scratch_bytes, pointwise_wgrad_scratch_bytes
 
+# The route selectors stay module globals under these names (not completion/op_config.py): bench.py, the tools and
+# several tests assign them, and the planners read them at call time.
 MAX_COUT = 64   # mvp_pointwise_wgrad's limit
 MAX_CIN = 64
 # Channel minimum of the MFMA route.  Rounds 2-3: 32 (below it a 32-wide MFMA block is mostly padding).  Round 4: 1 -- the
@@ -41,12 +71,13 @@ USE_MFMA = True            # False: nothing is routed to the MFMA kernels (the l
 MFMA_TRAIN = True          # under autograd the routed layers go through _PointwiseConv
 MFMA_DGRAD = True          # data gradient on mvp_pointwise_mfma (W^T, ReLU' on load)
 MFMA_WGRAD_MIN_CIN = 1     # weight gradient on mvp_pointwise_wgrad_mfma from this many input channels
+MFMA_WGRAD_MIN_POSITIONS = 16384   # B * L below this: too few slabs of positions to deal out (ECG's 64- and 256-point levels)
 # Round 6: what "the library" is for a float32 CUDA layer our kernels leave to it -- batched GEMMs (rocBLAS / hipBLASLt
 # through torch.matmul), not MIOpen's convolutions: a 1x1 convolution IS a GEMM per cloud; MIOpen wraps it in NHWC
 # transposes, starts every process on its naive reference kernels (5.4 ms per weight gradient of ECG's bottleneck layers for
 # the first ~150 steps) until its solver search settles on a different kernel from run to run, and its implicit-GEMM
 # backward-data kernel reads out of bounds on odd shapes (profiles/r6_miopen_igemm_bwd_fault.txt; that one is avoided either
-# way: _PointwiseConv.backward).  Measured (tools/ab_flag.py, 12 alternations, ECG -- the model with library-routed layers):
+# way: the `gemm` data gradient).  Measured (tools/ab_flag.py, 12 alternations, ECG -- the model with library-routed layers):
 # first alternation 23.9 -> 18.5 ms (no naive-kernel phase), steady state 16.94 = 16.93 ms in rounds 3-6 but 17.2 -> 17.55 in
 # rounds 8-12; VRCNet 18.39 -> 18.45.  Not faster, so the default stays MIOpen for the forward and the weight gradient of
 # those layers; True = no MIOpen call at all in the training path.
@@ -64,9 +95,37 @@ def _wgrad_scratch(device, nbytes):
     return buf
 
 
-MFMA_WGRAD_MIN_POSITIONS = 16384   # B * L below this: too few slabs of positions to deal out (ECG's 64- and 256-point levels)
+# ---- the layer's description: every dtype, layout and alignment test of this module is in the next three functions --------------------
+Layer = namedtuple("Layer", "cuda f32 dim B cin cout L x_dense w_dense x_aligned w_aligned nonempty")
 
 
+def _describe(x, weight):
+    """What the planners need to know about y = W x: device, dtypes (x and the weight float32), x.dim(), clouds, channels,
+    positions per cloud, x / the weight contiguous, x / the weight 16-byte aligned (the kernels' vector loads), x not empty."""
+    nonempty = x.numel() > 0
+    return Layer(x.is_cuda, x.dtype == torch.float32 and weight.dtype == torch.float32, x.dim(), x.size(0), weight.size(1),
+                 weight.size(0), x[0, 0].numel() if nonempty else 0, x.is_contiguous(), weight.is_contiguous(),
+                 x.data_ptr() % 16 == 0, weight.data_ptr() % 16 == 0, nonempty)
+
+
+def _float32(*tensors):
+    """The optional operands of the fused epilogue (residual, cloud_bias) are ones the kernel takes?"""
+    return all(t is None or t.dtype == torch.float32 for t in tensors)
+
+
+def _dense_grad(g):
+    """grad_out as every backward route reads it: contiguous and 16-byte aligned -- a clone where it is a view at an odd
+    offset (allocator blocks are aligned)."""
+    g = g.contiguous()
+    return g if g.data_ptr() % 16 == 0 else g.clone()
+
+
+def _densified(d):
+    """The description of (x.contiguous(), weight.contiguous()): a copy is a fresh, aligned block."""
+    return d._replace(x_dense=True, w_dense=True, x_aligned=d.x_aligned or not d.x_dense, w_aligned=d.w_aligned or not d.w_dense)
+
+
+# ---- the planners: pure functions of a Layer, what needs a gradient and the selectors above ------------------------------------
 def _gemm_fits(batch, m, k, length):
     """Per-cloud GEMM (m x k) (k x length) worth running on mvp_pointwise_mfma?  Not with a long
     reduction and fewer workgroups (128 x 128 tiles of the output) than the chip holds at once, or a
@@ -81,26 +140,128 @@ def _gemm_fits(batch, m, k, length):
     return -(-m // bm) * -(-length // 128) * batch >= 512
 
 
-def _mfma_fwd(x, cin, cout, weight=None):
-    """Forward GEMM through mvp_pointwise_mfma?"""
-    return _mfma_ok(x, cin, cout, weight) \
-        and _gemm_fits(x.size(0), cout, cin, x[0, 0].numel()) and (cout >= 32 or cin <= MFMA_SKINNY_FWD_MAX_CIN)
+def _ours(d):
+    return d.cuda and d.f32 and d.dim in (3, 4) and d.L > 0 and d.L % 4 == 0 and d.B <= 65535
 
 
-def _mfma_ok(x, cin, cout, weight=None):
-    """Shape / layout covered by the MFMA kernels?  (`weight`: the kernels read it with 16-byte
-    loads -- a parameter that is a view at an odd offset of a flattened / bucketed storage falls
-    back to the library convolution instead of failing with MVP_EBADARG.)"""
-    if not (USE_MFMA and x.is_cuda and x.dtype == torch.float32 and x.dim() in (3, 4) and x.is_contiguous()):
-        return False
-    if weight is not None and (weight.data_ptr() % 16 != 0 or not weight.is_contiguous()):
-        return False
-    length = x[0, 0].numel() if x.numel() else 0
-    return cin >= MFMA_MIN_CH and cout >= MFMA_MIN_CH and length > 0 and length % 4 == 0 and x.size(0) <= 65535 \
-        and x.data_ptr() % 16 == 0
+def _small(d):
+    """mvp_pointwise_wgrad / mvp_pointwise_dgrad take the layer's shape (the layout of x is the weight gradient's business)."""
+    return _ours(d) and 0 < d.cin <= MAX_CIN and 0 < d.cout <= MAX_COUT
 
 
+def _mfma(d, x_too=True):
+    """The MFMA kernels take the layer (16-byte loads: a parameter that is a view at an odd offset of a flattened /
+    bucketed storage goes to the library instead of failing with MVP_EBADARG).  x_too=False: the operand is not x (the
+    data gradient reads grad_out, which _dense_grad has made dense)."""
+    return USE_MFMA and _ours(d) and d.w_dense and d.w_aligned and d.cin >= MFMA_MIN_CH and d.cout >= MFMA_MIN_CH \
+        and (not x_too or (d.x_dense and d.x_aligned))
+
+
+def _mfma_fwd(d):
+    return _mfma(d) and _gemm_fits(d.B, d.cout, d.cin, d.L) and (d.cout >= 32 or d.cin <= MFMA_SKINNY_FWD_MAX_CIN)
+
+
+ConvPlan = namedtuple("ConvPlan", "via fwd layer")     # layer: what _PointwiseConv saves for its backward plan
+BackwardPlan = namedtuple("BackwardPlan", "dgrad wgrad premask wgrad_bytes")
+MaxPlan = namedtuple("MaxPlan", "via fwd layer")
+
+
+def _plan_conv(d, wants_grad):
+    """pointwise_conv: via `function` (_PointwiseConv), `autograd` (the library's convolution, differentiated by PyTorch) or
+    `none` (no gradient wanted); forward `mfma` or `library`."""
+    routed = d.cuda and d.f32 and d.x_dense and d.w_dense and d.nonempty and (_mfma(d) or _small(d))
+    if wants_grad and ((routed and (MFMA_TRAIN or _small(d))) or (not routed and USE_MFMA and d.cuda and d.f32 and d.nonempty)):
+        # (not routed: shapes no kernel of ours covers -- positions not a multiple of 4, strided tensors: the library's forward,
+        # but STILL _PointwiseConv's backward: its data gradient is a batched GEMM, never MIOpen's implicit-GEMM backward-data
+        # kernel, which reads out of bounds on such shapes)
+        d = _densified(d)
+        return ConvPlan("function", "mfma" if (MFMA_TRAIN or _small(d)) and _mfma_fwd(d) else "library", d)
+    if wants_grad or not USE_MFMA:
+        return ConvPlan("autograd", "library", d)
+    return ConvPlan("none", "mfma" if routed and _mfma_fwd(d) else "library", d)
+
+
+def _plan_conv_backward(d, relu, has_bias, need_x, need_w, need_b):
+    """_PointwiseConv.backward from the Layer saved at forward time: data gradient `small` / `mfma` / `gemm`, weight (+ bias)
+    gradient `mfma` / `small` / `gemm` / `miopen` (None: not needed), whether grad_out is masked by ReLU' up front for the
+    routes that do not mask on load, and the MFMA weight gradient's scratch size (queried once, here)."""
+    dgrad = wgrad = None
+    nbytes = 0
+    if need_x:
+        # <= 64 x 64 channels: mvp_pointwise_dgrad (11-26 us, at or below the MFMA kernel)
+        dgrad = "small" if _small(d) else \
+            "mfma" if MFMA_DGRAD and _mfma(d, x_too=False) and d.cin % 4 == 0 and _gemm_fits(d.B, d.cin, d.cout, d.L) else "gemm"
+    if need_w or need_b:
+        if d.cin >= MFMA_WGRAD_MIN_CIN and _mfma(d) and not _small(d) and d.B * d.L >= MFMA_WGRAD_MIN_POSITIONS:
+            nbytes = pointwise_wgrad_mfma_scratch_bytes(d.B, d.cin, d.cout, d.L, has_bias)
+        # (the library = GEMMs, see LIBRARY_IS_GEMM; MIOpen's weight-gradient kernels only with the switch off)
+        wgrad = "mfma" if nbytes > 0 else "small" if _small(d) and d.x_aligned else "gemm" if LIBRARY_IS_GEMM or d.L % 4 != 0 else "miopen"
+    premask = relu and (dgrad in ("small", "gemm") or wgrad in ("small", "gemm", "miopen"))
+    return BackwardPlan(dgrad, wgrad, premask, nbytes)
+
+
+def _plan_fused(d, need_x, relu=False, residual=False, float32_operands=True):
+    """pointwise_conv_fused: `fused` -- all three passes of the layer on the MFMA kernels (the fused prologues / epilogues live
+    there only), one GEMM -- or `composed`.  relu with a residual is composed: the fused backward masks by the final output,
+    which is not the inner ReLU's mask there."""
+    # (the skinny-forward rule of _mfma_fwd is not applied: 544 -> 16 at 384 points costs 0.031 ms here against the
+    # library's 0.024, the passes over the 53 MB input that the fused prologue saves cost 0.06)
+    ok = _mfma(d) and not (relu and residual) and float32_operands and _gemm_fits(d.B, d.cout, d.cin, d.L) \
+        and (not need_x or (d.cin % 4 == 0 and _gemm_fits(d.B, d.cin, d.cout, d.L))) \
+        and d.B * d.L >= MFMA_WGRAD_MIN_POSITIONS and pointwise_wgrad_mfma_scratch_bytes(d.B, d.cin, d.cout, d.L, True) > 0
+    return "fused" if ok else "composed"
+
+
+def _fused_routes(x, weight, need_x):
+    """All three passes of a layer on the MFMA kernels?  (_plan_fused on tensors.)"""
+    return _plan_fused(_describe(x, weight), need_x) == "fused"
+
+
+def _plan_dual(d1, d2, need_x):
+    """pointwise_conv_dual: `stacked` (one GEMM over both weights, two outputs) or `separate`."""
+    ok = d1.cout % 32 == 0 and _plan_fused(d1, need_x) == "fused" and _plan_fused(d2, need_x) == "fused" \
+        and _mfma_fwd(d1._replace(cout=d1.cout + d2.cout))
+    return "stacked" if ok else "separate"
+
+
+def _max_kernel_covers(d):
+    """Shapes mvp_pointwise_max_backward takes: its per-cloud sort of the winners lives in LDS ((3 Cout + L) * 4 <= 30000
+    bytes: L <= 4428 positions at Cout = 1024)."""
+    return d.cuda and d.f32 and d.L <= 16384 and d.cout <= 4096 and (3 * d.cout + d.L) * 4 <= 30000 and d.B <= 65535
+
+
+def _plan_max(d, wants_grad):
+    """pointwise_conv_max: via `function` (_PointwiseConvMax: the sparse backward pass), `autograd` (conv + max, dense) or
+    `none`; forward `fused` (the max inside the GEMM's epilogue) or `conv_max`."""
+    via = "none" if not wants_grad else "function" if not d.cuda or _max_kernel_covers(d) else "autograd"
+    fused = via != "autograd" and d.cuda and d.f32 and d.w_dense and d.nonempty and _mfma_fwd(d)
+    return MaxPlan(via, "fused" if fused else "conv_max", d)
+
+
+def _plan_max_backward(d):
+    """_PointwiseConvMax.backward, d describing the flattened operands: the `sparse` kernel or the same two index passes in
+    `torch` (host tensors / other dtypes -- the CPU tests; CUDA float32 shapes the kernel does not cover never get here:
+    this formulation's expanded index tensors would cost more than the dense GEMMs)."""
+    return "sparse" if _max_kernel_covers(d) and d.x_dense and d.w_dense else "torch"
+
+
+# ---- the kernels behind the routes ----------------------------------------------------------------------------------------------
 PW_RELU, PW_RELU_AFTER, PW_RES_IS_MASK, PW_X_RELU = 1, 2, 4, 8     # include/mvpops.h MVP_PW_*
+
+
+def _rows_of_4(w2d, cin):
+    """(w2d, ldw): rows padded to a multiple of 4 floats where cin is none -- the kernel reads the weight with 16-byte loads
+    (PCN's 1029 -> 512 folding layer at 16384 points: 5.49 -> 4.7 ms; the copy is 2 MB)."""
+    if cin % 4:
+        w2d = F.pad(w2d, (0, -cin % 4))
+    return w2d, w2d.size(1) if cin % 4 else 0
+
+
+def _one_bias(bias, cloud_bias):
+    """The epilogue's one addend per output: cloud_bias (B, Cout) (+ bias), else the bias."""
+    if cloud_bias is None:
+        return bias
+    return cloud_bias if bias is None else cloud_bias + bias          # (B, Cout): tiny
 
 
 def mfma_linear(x, w2d, bias=None, relu=False, residual=None, group=1, w_kmajor=False, xmask=None, x_relu=False,
@@ -125,12 +286,7 @@ def mfma_linear(x, w2d, bias=None, relu=False, residual=None, group=1, w_kmajor=
         y = torch.empty((B, cout) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
     else:
         y = torch.empty(B, cout, length // group, dtype=torch.float32, device=x.device)
-    ldw = 0
-    if not w_kmajor and cin % 4 != 0:
-        # rows padded to a multiple of 4 floats: the kernel reads the weight with 16-byte loads (PCN's 1029 -> 512
-        # folding layer at 16384 points: 5.49 -> 4.7 ms; the copy is 2 MB)
-        w2d = F.pad(w2d, (0, -cin % 4))
-        ldw = w2d.size(1)
+    w2d, ldw = (w2d, 0) if w_kmajor else _rows_of_4(w2d, cin)
     flags = (PW_RELU if relu else 0) | (PW_RELU_AFTER if relu_after else 0) | (PW_RES_IS_MASK if res_is_mask else 0) \
         | (PW_X_RELU if x_relu else 0)
     call("mvp_pointwise_mfma_ex", x.device, B, cin, cout, length, x, xmask, w2d, ldw, int(w_kmajor), bias, int(bias_per_cloud),
@@ -138,13 +294,15 @@ def mfma_linear(x, w2d, bias=None, relu=False, residual=None, group=1, w_kmajor=
     return (y, y2) if m_split else y
 
 
-def mfma_wgrad(x, gy, cout, cin, with_bias, gymask=None, x_relu=False):
+def mfma_wgrad(x, gy, cout, cin, with_bias, gymask=None, x_relu=False, nbytes=None):
     """(gw (Cout, Cin), gb (Cout) | None) of y = W x + b from x (B, Cin, ...) and gy (B, Cout, ...);
     with gymask, gy counts as 0 where gymask <= 0 (aten.threshold_backward's select: gy passes where gymask is NaN); with
-    x_relu, x counts as relu(x), a NaN staying a NaN (mvp_pointwise_wgrad_mfma_ex)."""
+    x_relu, x counts as relu(x), a NaN staying a NaN (mvp_pointwise_wgrad_mfma_ex).  nbytes: the kernel's scratch size
+    where the caller's plan has queried it already."""
     B = x.size(0)
     length = x[0, 0].numel()
-    nbytes = pointwise_wgrad_mfma_scratch_bytes(B, cin, cout, length, with_bias)
+    if nbytes is None:
+        nbytes = pointwise_wgrad_mfma_scratch_bytes(B, cin, cout, length, with_bias)
     scratch = _wgrad_scratch(x.device, nbytes)     # stream-ordered reuse: the reduce kernel has read it before the next call writes
     gw = torch.empty(cout, cin, dtype=torch.float32, device=x.device)
     gb = torch.empty(cout, dtype=torch.float32, device=x.device) if with_bias else None
@@ -152,47 +310,30 @@ def mfma_wgrad(x, gy, cout, cin, with_bias, gymask=None, x_relu=False):
     return gw, gb
 
 
-def _covered(x, weight):
-    if not (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.dim() in (3, 4)):
-        return False
-    if x.numel() == 0 or weight.numel() == 0:
-        return False
-    length = x[0, 0].numel()
-    return weight.size(0) <= MAX_COUT and weight.size(1) <= MAX_CIN and length % 4 == 0 and length > 0 \
-        and x.size(0) <= 65535
-
-
-def _library_conv(x, weight, bias):
+def _library_conv(x, weight, bias, d):
     """The layer on the library, no autograd: conv1d / conv2d (MIOpen) or, with LIBRARY_IS_GEMM on float32 CUDA tensors, one
     batched GEMM W x[b] (+ bias through baddbmm's addend)."""
-    if LIBRARY_IS_GEMM and x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32:
-        cout, cin = weight.shape[:2]
+    if LIBRARY_IS_GEMM and d.cuda and d.f32:
         x3 = x.flatten(2)
-        w3 = weight.reshape(1, cout, cin).expand(x.size(0), cout, cin)
-        y = torch.bmm(w3, x3) if bias is None else torch.baddbmm(bias.view(1, cout, 1), w3, x3)
-        return y.view((x.size(0), cout) + tuple(x.shape[2:]))
-    return (F.conv1d if x.dim() == 3 else F.conv2d)(x, weight, bias)
+        w3 = weight.reshape(1, d.cout, d.cin).expand(d.B, d.cout, d.cin)
+        y = torch.bmm(w3, x3) if bias is None else torch.baddbmm(bias.view(1, d.cout, 1), w3, x3)
+        return y.view((d.B, d.cout) + tuple(x.shape[2:]))
+    return (F.conv1d if d.dim == 3 else F.conv2d)(x, weight, bias)
 
 
 class _PointwiseConv(Function):
-    """y = [relu](W x + bias): forward and data gradient on the MFMA GEMM where the
-    shape allows, the small-channel weight gradient through mvp_pointwise_wgrad, the
-    rest through the library's convolution passes."""
+    """y = [relu](W x + bias) on the routes of a ConvPlan (forward) and of _plan_conv_backward."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, relu):
-        conv = F.conv1d if x.dim() == 3 else F.conv2d
-        cout, cin = weight.shape[:2]
+    def forward(ctx, x, weight, bias, relu, plan):
+        d = ctx.layer = plan.layer
         ctx.has_bias = bias is not None
         ctx.relu = relu
-        if not x.is_contiguous():          # (a permuted view: the kernels of the backward pass take dense tensors)
-            x = x.contiguous()
-        if not weight.is_contiguous():
-            weight = weight.contiguous()
-        if (MFMA_TRAIN or _covered(x, weight)) and _mfma_fwd(x, cin, cout, weight):
-            y = mfma_linear(x, weight.view(cout, cin), bias, relu=relu)
+        x, weight = x.contiguous(), weight.contiguous()     # (a permuted view: the kernels of the backward pass take dense tensors)
+        if plan.fwd == "mfma":
+            y = mfma_linear(x, weight.view(d.cout, d.cin), bias, relu=relu)
         else:
-            y = _library_conv(x, weight, bias)
+            y = _library_conv(x, weight, bias, d)
             if relu:
                 y = torch.relu_(y)
         ctx.save_for_backward(x, weight, y if relu else None)
@@ -201,103 +342,68 @@ class _PointwiseConv(Function):
     @staticmethod
     def backward(ctx, grad_out):
         x, weight, y = ctx.saved_tensors
-        cout, cin = weight.shape[:2]
-        nd = x.dim() - 2
-        gy = grad_out.contiguous()
-        need_x = ctx.needs_input_grad[0]
-        need_w = ctx.needs_input_grad[1]
+        d = ctx.layer
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         need_b = ctx.has_bias and ctx.needs_input_grad[2]
-        gx_small = need_x and _covered(x, weight)          # <= 64 x 64 channels: mvp_pointwise_dgrad (11-26 us, at or below the MFMA kernel)
-        gx_mfma = MFMA_DGRAD and need_x and not gx_small and _mfma_ok(gy, cout, cin, weight) and cin % 4 == 0 \
-            and _gemm_fits(x.size(0), cin, cout, x[0, 0].numel())
-        gw_mfma = (need_w or need_b) and cin >= MFMA_WGRAD_MIN_CIN and _mfma_ok(x, cin, cout, weight) and not _covered(x, weight) \
-            and x.size(0) * x[0, 0].numel() >= MFMA_WGRAD_MIN_POSITIONS \
-            and pointwise_wgrad_mfma_scratch_bytes(x.size(0), cin, cout, x[0, 0].numel(), ctx.has_bias) > 0
+        plan = _plan_conv_backward(d, ctx.relu, ctx.has_bias, need_x, need_w, need_b)
+        gy = _dense_grad(grad_out)
         # ReLU'(.): the MFMA kernels mask grad_out by the saved output on load; the other routes get
         # the masked tensor.  Every route takes threshold_backward's convention (0 where y <= 0, grad_out elsewhere -- what
         # autograd of torch.relu does): never a multiply, which would turn an Inf of grad_out at y <= 0 into NaN
         mask = y if ctx.relu else None
-        if ctx.relu and ((need_x and not gx_mfma) or ((need_w or need_b) and not gw_mfma)):
-            gy_masked = torch.ops.aten.threshold_backward(gy, y, 0)
-        else:
-            gy_masked = gy
+        gy_masked = torch.ops.aten.threshold_backward(gy, y, 0) if plan.premask else gy
         gx = gw = gb = None
-        if need_x:
-            if gx_mfma:
-                gx = mfma_linear(gy, weight.view(cout, cin), w_kmajor=True, xmask=mask)       # W^T (gy . relu')
-            elif _covered(x, weight) and gy_masked.data_ptr() % 16 == 0:
-                # few channels: W^T gy in one pass over gy (mvp_pointwise_dgrad) -- not the library's implicit-GEMM
-                # kernel, one variant of which reads out of bounds on these shapes (csrc/pointwise.hip)
-                gx = torch.empty_like(x)
-                call("mvp_pointwise_dgrad", x.device, x.size(0), cin, cout, x[0, 0].numel(), weight, gy_masked, gx)
-            else:
-                # W^T gy per cloud as a batched library GEMM -- NOT aten.convolution_backward: MIOpen's implicit-GEMM
-                # backward-data kernel (igemm_bwd_gtcx35_nhwc_fp32) reads past its operands on some of these shapes (37- and
-                # 50-point layers of the golden tests: a GPU memory fault whenever the neighbouring page happens to be
-                # unmapped -- rocgdb trace in profiles/NOTES_r6.md section 11); a 1x1 convolution's data gradient is a GEMM
-                gx = torch.matmul(weight.reshape(cout, cin).t(), gy_masked.flatten(2)).view_as(x)
-        gy = gy_masked
-        if need_w or need_b:
-            if gw_mfma:
-                gw, gb = mfma_wgrad(x, grad_out.contiguous(), cout, cin, ctx.has_bias, gymask=mask)
-                gw = gw.view_as(weight)
-            elif _covered(x, weight):
-                B = x.size(0)
-                length = x[0, 0].numel()
-                nbytes = pointwise_wgrad_scratch_bytes(B, cin, cout, length)
-                scratch = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-                gw = torch.empty_like(weight)
-                gb = torch.empty(cout, dtype=torch.float32, device=x.device) if ctx.has_bias else None
-                call("mvp_pointwise_wgrad", x.device, B, cin, cout, length, x, gy, gw, gb, scratch, nbytes)
-            elif LIBRARY_IS_GEMM or x[0, 0].numel() % 4 != 0 or not x.is_contiguous():
-                # (the library = GEMMs, see LIBRARY_IS_GEMM; MIOpen's weight-gradient kernels only with the switch off)
-                gw = torch.einsum("bol,bil->oi", gy.flatten(2), x.flatten(2)).view_as(weight) if need_w else None
-                gb = gy.flatten(2).sum((0, 2)) if need_b else None
-            else:
-                _, gw, gb = torch.ops.aten.convolution_backward(
-                    gy, x, weight, [cout] if ctx.has_bias else None, [1] * nd, [0] * nd, [1] * nd, False, [0] * nd, 1,
-                    [False, need_w, need_b])
-        return gx, gw, gb, None
+        if plan.dgrad == "mfma":
+            gx = mfma_linear(gy, weight.view(d.cout, d.cin), w_kmajor=True, xmask=mask)       # W^T (gy . relu')
+        elif plan.dgrad == "small":
+            # few channels: W^T gy in one pass over gy (mvp_pointwise_dgrad) -- not the library's implicit-GEMM
+            # kernel, one variant of which reads out of bounds on these shapes (csrc/pointwise.hip)
+            gx = torch.empty_like(x)
+            call("mvp_pointwise_dgrad", x.device, d.B, d.cin, d.cout, d.L, weight, gy_masked, gx)
+        elif plan.dgrad == "gemm":
+            # W^T gy per cloud as a batched library GEMM -- NOT aten.convolution_backward: MIOpen's implicit-GEMM
+            # backward-data kernel (igemm_bwd_gtcx35_nhwc_fp32) reads past its operands on some of these shapes (37- and
+            # 50-point layers of the golden tests: a GPU memory fault whenever the neighbouring page happens to be
+            # unmapped -- rocgdb trace in profiles/NOTES_r6.md section 11); a 1x1 convolution's data gradient is a GEMM
+            gx = torch.matmul(weight.reshape(d.cout, d.cin).t(), gy_masked.flatten(2)).view_as(x)
+        if plan.wgrad == "mfma":
+            gw, gb = mfma_wgrad(x, gy, d.cout, d.cin, ctx.has_bias, gymask=mask, nbytes=plan.wgrad_bytes)
+            gw = gw.view_as(weight)
+        elif plan.wgrad == "small":
+            nbytes = pointwise_wgrad_scratch_bytes(d.B, d.cin, d.cout, d.L)
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+            gw = torch.empty_like(weight)
+            gb = torch.empty(d.cout, dtype=torch.float32, device=x.device) if ctx.has_bias else None
+            call("mvp_pointwise_wgrad", x.device, d.B, d.cin, d.cout, d.L, x, gy_masked, gw, gb, scratch, nbytes)
+        elif plan.wgrad == "gemm":
+            gw = torch.einsum("bol,bil->oi", gy_masked.flatten(2), x.flatten(2)).view_as(weight) if need_w else None
+            gb = gy_masked.flatten(2).sum((0, 2)) if need_b else None
+        elif plan.wgrad == "miopen":
+            nd = d.dim - 2
+            _, gw, gb = torch.ops.aten.convolution_backward(
+                gy_masked, x, weight, [d.cout] if ctx.has_bias else None, [1] * nd, [0] * nd, [1] * nd, False, [0] * nd, 1,
+                [False, need_w, need_b])
+        return gx, gw, gb, None, None
+
+
+def _wants_grad(*tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 
 
 def pointwise_conv(x, weight, bias=None, relu=False):
     """y = W x + bias (then ReLU if `relu`) over the channel dimension of x
     (B,Cin,N) / (B,Cin,H,W); weight (Cout,Cin,1[,1])."""
-    conv = F.conv1d if x.dim() == 3 else F.conv2d
-    cout, cin = weight.shape[:2]
-    routed = x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.is_contiguous() \
-        and weight.is_contiguous() and x.numel() > 0 and (_mfma_ok(x, cin, cout, weight) or _covered(x, weight))
-    wants_grad = torch.is_grad_enabled() and (weight.requires_grad or x.requires_grad or (bias is not None and bias.requires_grad))
-    if routed and wants_grad:
-        if MFMA_TRAIN or _covered(x, weight):
-            return _PointwiseConv.apply(x, weight, bias, relu)
-        y = conv(x, weight, bias)
-        return torch.relu(y) if relu else y
-    if wants_grad and USE_MFMA and x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.numel() > 0:
-        # shapes no kernel of ours covers (positions not a multiple of 4, strided tensors): the library's forward, but STILL
-        # _PointwiseConv's backward -- its data gradient is a batched GEMM, never MIOpen's implicit-GEMM backward-data kernel,
-        # which reads out of bounds on such shapes (see _PointwiseConv.backward)
-        return _PointwiseConv.apply(x, weight, bias, relu)
-    if routed and _mfma_fwd(x, cin, cout, weight):                 # inference
-        return mfma_linear(x, weight.view(cout, cin), bias, relu=relu)
-    y = _library_conv(x, weight, bias) if (USE_MFMA and not wants_grad) else conv(x, weight, bias)
+    d = _describe(x, weight)
+    plan = _plan_conv(d, _wants_grad(weight, x, bias))
+    if plan.via == "function":
+        return _PointwiseConv.apply(x, weight, bias, relu, plan)
+    if plan.fwd == "mfma":                 # inference
+        return mfma_linear(x, weight.view(d.cout, d.cin), bias, relu=relu)
+    if plan.via == "autograd":
+        y = (F.conv1d if d.dim == 3 else F.conv2d)(x, weight, bias)
+    else:
+        y = _library_conv(x, weight, bias, d)
     return torch.relu(y) if relu else y
-
-
-def _fused_routes(x, weight, need_x):
-    """All three passes of a layer on the MFMA kernels (the fused prologues / epilogues live there only)?"""
-    cout, cin = weight.shape[:2]
-    if not (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.is_contiguous()
-            and weight.is_contiguous() and x.numel() > 0 and _mfma_ok(x, cin, cout, weight)):
-        return False
-    B, length = x.size(0), x[0, 0].numel()
-    # (the skinny-forward rule of _mfma_fwd is not applied: 544 -> 16 at 384 points costs 0.031 ms here against the
-    # library's 0.024, the passes over the 53 MB input that the fused prologue saves cost 0.06)
-    if not _gemm_fits(B, cout, cin, length):
-        return False
-    if need_x and not (cin % 4 == 0 and _gemm_fits(B, cin, cout, length)):
-        return False
-    return B * length >= MFMA_WGRAD_MIN_POSITIONS and pointwise_wgrad_mfma_scratch_bytes(B, cin, cout, length, True) > 0
 
 
 class _PointwiseConvFused(Function):
@@ -306,18 +412,12 @@ class _PointwiseConvFused(Function):
     relational encoder (vrcnet.py:34-57, 151, 172, 283-296) cost no elementwise pass forward.  Backward: ONE pass masks
     grad_out by the output where a residual or a per-cloud bias needs the masked tensor itself (otherwise the GEMMs mask on
     load), the data gradient zeroes its output where x <= 0 in its epilogue (threshold_backward's convention like every
-    ReLU' here: it passes where x is NaN), the weight gradient takes relu(x) on load."""
+    ReLU' here: it passes where x is NaN), the weight gradient takes relu(x) on load.  (relu together with a residual never
+    gets here: _plan_fused.)"""
 
     @staticmethod
     def forward(ctx, x, weight, bias, cloud_bias, residual, relu_in, relu, relu_after):
-        cout, cin = weight.shape[:2]
-        b = bias
-        per_cloud = False
-        if cloud_bias is not None:
-            b = cloud_bias if bias is None else cloud_bias + bias          # (B, Cout): tiny
-            per_cloud = True
-        y = mfma_linear(x, weight.view(cout, cin), b, relu=relu, residual=residual, x_relu=relu_in, relu_after=relu_after,
-                        bias_per_cloud=per_cloud)
+        y = _fused_forward(x, weight, bias, cloud_bias, residual, relu_in, relu, relu_after)
         ctx.has_bias, ctx.has_cloud_bias, ctx.has_residual = bias is not None, cloud_bias is not None, residual is not None
         ctx.relu_in, ctx.relu_out = relu_in, relu or relu_after
         ctx.save_for_backward(x, weight, y if ctx.relu_out else None)
@@ -327,7 +427,7 @@ class _PointwiseConvFused(Function):
     def backward(ctx, grad_out):
         x, weight, y = ctx.saved_tensors
         cout, cin = weight.shape[:2]
-        gy = grad_out.contiguous()
+        gy = _dense_grad(grad_out)
         mask = None
         if ctx.relu_out:
             if ctx.has_residual or ctx.has_cloud_bias:
@@ -349,25 +449,28 @@ class _PointwiseConvFused(Function):
         return gx, gw, gb, gcb, gres, None, None, None
 
 
+def _fused_forward(x, weight, bias, cloud_bias, residual, relu_in, relu, relu_after):
+    cout, cin = weight.shape[:2]
+    return mfma_linear(x, weight.view(cout, cin), _one_bias(bias, cloud_bias), relu=relu, residual=residual, x_relu=relu_in,
+                       relu_after=relu_after, bias_per_cloud=cloud_bias is not None)
+
+
 def pointwise_conv_fused(x, weight, bias=None, relu_in=False, relu=False, residual=None, relu_after=False, cloud_bias=None):
     """act2(act1(W in(x) + bias + cloud_bias[b]) + residual): in = ReLU if relu_in, act1 = ReLU if relu, act2 = ReLU if
     relu_after; cloud_bias (B, Cout) (summed with the bias first: one addend per output), residual like the output.  One GEMM where all passes of the layer are on the MFMA
     kernels, the same function composed of pointwise_conv and elementwise passes elsewhere (host tensors, other dtypes,
     shapes the routing rules give to the library)."""
-    wants_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, bias, residual, cloud_bias))
-    if _fused_routes(x, weight, x.requires_grad and wants_grad) and (residual is None or residual.dtype == torch.float32):
-        if residual is not None and not residual.is_contiguous():
-            residual = residual.contiguous()
+    wants_grad = _wants_grad(x, weight, bias, residual, cloud_bias)
+    route = _plan_fused(_describe(x, weight), x.requires_grad and wants_grad, relu, residual is not None,
+                        _float32(residual, cloud_bias))
+    if route == "fused":
+        residual = None if residual is None else residual.contiguous()
+        cloud_bias = None if cloud_bias is None else cloud_bias.contiguous()
         if wants_grad:
             return _PointwiseConvFused.apply(x, weight, bias, cloud_bias, residual, relu_in, relu, relu_after)
-        cout, cin = weight.shape[:2]
-        b = bias
-        if cloud_bias is not None:
-            b = cloud_bias if bias is None else cloud_bias + bias
-        return mfma_linear(x, weight.view(cout, cin), b, relu=relu, residual=residual, x_relu=relu_in, relu_after=relu_after,
-                           bias_per_cloud=cloud_bias is not None)
+        return _fused_forward(x, weight, bias, cloud_bias, residual, relu_in, relu, relu_after)
     if cloud_bias is not None:
-        cb = cloud_bias if bias is None else cloud_bias + bias
+        cb = _one_bias(bias, cloud_bias)
         h = pointwise_conv(torch.relu(x) if relu_in else x, weight, None) + cb.view(cb.shape + (1,) * (x.dim() - 2))
         h = torch.relu_(h) if relu else h
     else:
@@ -377,6 +480,11 @@ def pointwise_conv_fused(x, weight, bias=None, relu_in=False, relu=False, residu
     return torch.relu(h) if relu_after else h
 
 
+def _stacked_forward(x, w1, w2):
+    c1, c2, cin = w1.size(0), w2.size(0), w1.size(1)
+    return mfma_linear(x, torch.cat((w1.view(c1, cin), w2.view(c2, cin)), 0), m_split=c1)
+
+
 class _PointwiseConvDual(Function):
     """(W1 x, W2 x) of ONE input as one GEMM with two contiguous outputs (mvp_pointwise_mfma_ex, m_split): a residual unit's
     conv1 / conv_res (vrcnet.py:160-172).  The stacked convolution of round 4 handed out torch.split views -- a copy for the
@@ -384,16 +492,14 @@ class _PointwiseConvDual(Function):
 
     @staticmethod
     def forward(ctx, x, w1, w2):
-        c1, c2, cin = w1.size(0), w2.size(0), w1.size(1)
-        y1, y2 = mfma_linear(x, torch.cat((w1.view(c1, cin), w2.view(c2, cin)), 0), m_split=c1)
         ctx.save_for_backward(x, w1, w2)
-        return y1, y2
+        return _stacked_forward(x, w1, w2)
 
     @staticmethod
     def backward(ctx, g1, g2):
         x, w1, w2 = ctx.saved_tensors
         c1, c2, cin = w1.size(0), w2.size(0), w1.size(1)
-        g1, g2 = g1.contiguous(), g2.contiguous()
+        g1, g2 = _dense_grad(g1), _dense_grad(g2)
         gx = None
         if ctx.needs_input_grad[0]:
             gx = mfma_linear(g1, w1.view(c1, cin), w_kmajor=True)
@@ -405,15 +511,11 @@ class _PointwiseConvDual(Function):
 
 def pointwise_conv_dual(x, w1, w2):
     """(conv(x, w1), conv(x, w2)), bias-free, both contiguous; one pass over x where the MFMA kernels cover the layer."""
-    c1, c2, cin = w1.size(0), w2.size(0), w1.size(1)
-    need_x = torch.is_grad_enabled() and x.requires_grad
-    stacked_ok = c1 % 32 == 0 and w1.is_contiguous() and w2.is_contiguous() and x.is_cuda \
-        and _fused_routes(x, w1, need_x) and _fused_routes(x, w2, need_x) and _mfma_fwd(x, cin, c1 + c2, None)
-    if not stacked_ok:
+    if _plan_dual(_describe(x, w1), _describe(x, w2), torch.is_grad_enabled() and x.requires_grad) == "separate":
         return pointwise_conv(x, w1), pointwise_conv(x, w2)
-    if torch.is_grad_enabled() and (x.requires_grad or w1.requires_grad or w2.requires_grad):
+    if _wants_grad(x, w1, w2):
         return _PointwiseConvDual.apply(x, w1, w2)
-    return mfma_linear(x, torch.cat((w1.view(c1, cin), w2.view(c2, cin)), 0), m_split=c1)
+    return _stacked_forward(x, w1, w2)
 
 
 class _PointwiseConvMax(Function):
@@ -426,14 +528,9 @@ class _PointwiseConvMax(Function):
     reports); tests/test_harness_cpu.py::test_pointwise_conv_max_matches_autograd."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias):
+    def forward(ctx, x, weight, bias, plan):
         with torch.no_grad():
-            fused = mfma_conv_max(x, weight, bias)
-            if fused is not None:
-                val, idx = fused
-            else:
-                y = pointwise_conv(x, weight, bias)
-                val, idx = y.flatten(2).max(dim=2)
+            val, idx = _conv_max_forward(x, weight, bias, plan)
         ctx.save_for_backward(x, weight, idx)
         ctx.has_bias = bias is not None
         return val
@@ -445,12 +542,12 @@ class _PointwiseConvMax(Function):
         cout = weight.size(0)
         x3 = x.reshape(B, cin, -1)
         w2 = weight.reshape(cout, cin)
-        g = g.contiguous()
+        g = _dense_grad(g)
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         need_b = ctx.has_bias and ctx.needs_input_grad[2]
         length = x3.size(2)
         gx = gw = gb = None
-        if _conv_max_kernel_covers(x, weight) and g.dtype == torch.float32 and x3.is_contiguous() and w2.is_contiguous():
+        if _plan_max_backward(_describe(x3, w2)) == "sparse":
             gx = torch.empty_like(x3) if need_x else None
             gw = torch.empty_like(w2) if (need_w or need_b) else None
             gb = torch.empty(cout, dtype=torch.float32, device=x.device) if need_b else None
@@ -458,10 +555,7 @@ class _PointwiseConvMax(Function):
             scratch = _wgrad_scratch(x.device, nbytes) if nbytes else None     # the winning columns of x, staged
             call("mvp_pointwise_max_backward", x.device, B, cin, cout, length, x3, w2, g, idx.int(), gx, gw, gb, scratch,
                  nbytes)
-            return (gx.view_as(x) if need_x else None, gw.view_as(weight) if need_w else None, gb)
-        # host tensors / other dtypes (the CPU tests): the same two index passes in PyTorch.  CUDA float32 shapes the
-        # kernel does not cover never get here (pointwise_conv_max routes them to conv + max under plain autograd: this
-        # formulation's expanded index tensors would cost more than the dense GEMMs)
+            return (gx.view_as(x) if need_x else None, gw.view_as(weight) if need_w else None, gb, None)
         where = idx.unsqueeze(1).expand(B, cin, cout)                  # [b, ci, co] -> winning position of (b, co)
         if need_x:
             gx = torch.zeros_like(x3).scatter_add_(2, where, g.unsqueeze(1) * w2.t().unsqueeze(0)).view_as(x)
@@ -469,37 +563,31 @@ class _PointwiseConvMax(Function):
             gw = torch.einsum("bo,bio->oi", g, torch.gather(x3, 2, where)).view_as(weight)
         if need_b:
             gb = g.sum(0)
-        return gx, gw, gb
+        return gx, gw, gb, None
+
+
+def _mfma_max(x, weight, bias, d):
+    w2d, ldw = _rows_of_4(weight.reshape(d.cout, d.cin), d.cin)
+    val = torch.empty(d.B, d.cout, dtype=torch.float32, device=x.device)
+    idx = torch.empty(d.B, d.cout, dtype=torch.int32, device=x.device)
+    keys = torch.empty(d.B * d.cout, dtype=torch.int64, device=x.device)
+    call("mvp_pointwise_mfma_max", x.device, d.B, d.cin, d.cout, d.L, x, w2d, ldw, bias, 0, val, idx, keys, keys.numel() * 8)
+    return val, idx
 
 
 def mfma_conv_max(x, weight, bias=None):
     """(values (B, Cout), positions (B, Cout) int32) of (W x + bias).max over the positions inside the GEMM's epilogue
     (mvp_pointwise_mfma_max: the (B, Cout, L) tensor is never written), or None where the forward GEMM is not routed to
     the MFMA kernel.  No autograd."""
-    cout, cin = weight.size(0), weight.size(1)
-    if not (x.is_cuda and weight.dtype == torch.float32 and weight.is_contiguous() and x.numel() > 0
-            and _mfma_fwd(x, cin, cout, weight)):
-        return None
-    B, length = x.size(0), x[0, 0].numel()
-    w2d = weight.reshape(cout, cin)
-    ldw = 0
-    if cin % 4 != 0:
-        w2d = F.pad(w2d, (0, -cin % 4))
-        ldw = w2d.size(1)
-    val = torch.empty(B, cout, dtype=torch.float32, device=x.device)
-    idx = torch.empty(B, cout, dtype=torch.int32, device=x.device)
-    keys = torch.empty(B * cout, dtype=torch.int64, device=x.device)
-    call("mvp_pointwise_mfma_max", x.device, B, cin, cout, length, x, w2d, ldw, bias, 0, val, idx, keys, keys.numel() * 8)
-    return val, idx
+    plan = _plan_max(_describe(x, weight), False)
+    return _mfma_max(x, weight, bias, plan.layer) if plan.fwd == "fused" else None
 
 
-def _conv_max_kernel_covers(x, weight):
-    """Shapes mvp_pointwise_max_backward takes: its per-cloud sort of the winners lives in LDS ((3 Cout + L) * 4 <= 30000
-    bytes: L <= 4428 positions at Cout = 1024)."""
-    cout = weight.size(0)
-    length = x[0, 0].numel() if x.numel() else 0
-    return x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and length <= 16384 and cout <= 4096 \
-        and (3 * cout + length) * 4 <= 30000 and x.size(0) <= 65535
+def _conv_max_forward(x, weight, bias, plan):
+    """(values, positions) on the forward route of a MaxPlan."""
+    if plan.fwd == "fused":
+        return _mfma_max(x, weight, bias, plan.layer)
+    return pointwise_conv(x, weight, bias).flatten(2).max(dim=2)
 
 
 _conv_max_uncovered_seen = set()
@@ -507,20 +595,18 @@ _conv_max_uncovered_seen = set()
 
 def pointwise_conv_max(x, weight, bias=None):
     """(W x + bias).max over the positions: x (B,Cin,N) / (B,Cin,H,W), weight (Cout,Cin,1[,1]) -> (B, Cout)."""
-    if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
-        if not x.is_cuda or _conv_max_kernel_covers(x, weight):
-            return _PointwiseConvMax.apply(x, weight, bias)
-        shape = (weight.size(0), x[0, 0].numel())
+    d = _describe(x, weight)
+    plan = _plan_max(d, _wants_grad(x, weight, bias))
+    if plan.via == "function":
+        return _PointwiseConvMax.apply(x, weight, bias, plan)
+    if plan.via == "autograd":
+        shape = (d.cout, d.L)
         if shape not in _conv_max_uncovered_seen:          # (once per shape)
             _conv_max_uncovered_seen.add(shape)
             import logging
             logging.getLogger(__name__).info("conv -> max over %d positions x %d channels: outside the sparse backward kernel's "
                                              "LDS budget, dense autograd route", shape[1], shape[0])
-        return pointwise_conv(x, weight, bias).flatten(2).max(dim=2)[0]      # (plain autograd)
-    fused = mfma_conv_max(x, weight, bias)                                     # no gradient wanted: the fused forward alone
-    if fused is not None:
-        return fused[0]
-    return pointwise_conv(x, weight, bias).flatten(2).max(dim=2)[0]
+    return _conv_max_forward(x, weight, bias, plan)[0]      # (plain autograd, or no gradient wanted: the forward alone)
 
 
 class PointwiseConv1d(nn.Conv1d):

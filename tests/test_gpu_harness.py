@@ -698,7 +698,8 @@ def test_pointwise_conv_fused_matches_the_composed_ops_under_autograd(B, cin, co
     assert pw._fused_routes(x, w, True) == (cin % 4 == 0)
     cases = [dict(relu_in=True), dict(relu_in=True, relu=True), dict(relu_in=True, residual=res, relu_after=True),
              dict(residual=res, relu_after=True), dict(residual=res), dict(relu=True, cloud_bias=cb), dict(cloud_bias=cb),
-             dict(relu_in=True, relu=True, bias=None)]
+             dict(relu_in=True, relu=True, bias=None), dict(relu=True, residual=res),
+             dict(relu=True, residual=res, relu_after=True)]
     for kw in cases:
         bias = kw.pop("bias", b)
         inputs = [t for t in (x, w, bias, kw.get("residual"), kw.get("cloud_bias")) if t is not None]
