@@ -148,173 +148,22 @@ __global__ __launch_bounds__(kCdThreads) void nm_distance_kernel(
 
 // ---------------------------------------------------------------------------
 // Spatially sorted variant for large clouds: the same result with most of the
-// B*N*M pairs never evaluated.
-//
-// (1) chamfer_sort_kernel buckets each cloud side into 16^3 Morton-ordered
-//     cells (counting sort in LDS) and writes, into caller-provided scratch,
-//     the points in that order as float4 {x, y, z, bits(original index)}, the
-//     bounding box of every run of 16 sorted points (a "tile") and of every run
-//     of 1024 (a "batch").
-// (2) nm_distance_sorted_kernel keeps the brute-force skeleton -- a lane owns Q
-//     queries, candidates stream through LDS batches -- but both sides are in
-//     Morton order, so the 64*Q queries of a wave sit in a small box and a
-//     tile / batch is SKIPPED when the distance between that box and the
-//     tile's box already exceeds the worst current best of the wave.  Batches
-//     are visited outwards from the query block's own position in the order,
-//     so the bests are tight after the first batch or two.
-// Exactness: the box distance uses the same subtract / fma chain as sqdist3 on
-// per-axis gaps that are <= every member pair's |difference| (float subtract,
-// multiply and fma are monotone), so it never exceeds a member pair's computed
-// distance, and a tile is skipped only on strict `>`: a candidate that equals
-// the current best is still evaluated.  Ties go to the lowest ORIGINAL index
-// (chamfer3D.cu:36,46,126) by minimising the key {distance bits, original
-// index} -- the visiting order no longer is the index order.
-__device__ __forceinline__ int cs_spread4(int v) {  // bit i -> bit 3i
-  v &= 0xF;
-  v = (v | (v << 4)) & 0xC3;
-  v = (v | (v << 2)) & 0x249;
-  return v;
-}
-
-__global__ __launch_bounds__(kCsThreads) void chamfer_sort_kernel(
-    int n1, int n2, const float *__restrict__ xyz1, const float *__restrict__ xyz2,
-    char *__restrict__ scratch) {
-  const int side = blockIdx.x, cloud = blockIdx.y;
-  const int cnt = side == 0 ? n1 : n2;
-  const long long per_cloud = cs_side_bytes(n1) + cs_side_bytes(n2);
-  const CsSide out = cs_carve(scratch + (size_t)cloud * per_cloud + (side ? cs_side_bytes(n1) : 0), cnt);
-  const float *__restrict__ in = (side == 0 ? xyz1 : xyz2) + (size_t)cloud * cnt * 3;
-  const int cp = (int)cs_round_up(cnt);
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-
-  __shared__ int s_cnt[kCsCells];
-  __shared__ int s_start[kCsCells];
-  __shared__ float s_red[6][kCsThreads / 64];
-  __shared__ int s_wsum[kCsThreads / 64];
-
-  // bounding box
-  float mn[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
-  float mx[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-  for (int k = t; k < cnt; k += kCsThreads) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const float v = in[k * 3 + a];
-      mn[a] = __builtin_fminf(mn[a], v);
-      mx[a] = __builtin_fmaxf(mx[a], v);
-    }
-  }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      mn[a] = __builtin_fminf(mn[a], __shfl_xor(mn[a], off, 64));
-      mx[a] = __builtin_fmaxf(mx[a], __shfl_xor(mx[a], off, 64));
-    }
-    if (lane == 0) {
-      s_red[a][wave] = mn[a];
-      s_red[3 + a][wave] = mx[a];
-    }
-  }
-  for (int c = t; c < kCsCells; c += kCsThreads) s_cnt[c] = 0;
-  __syncthreads();
-  float lo[3], ext = 0.f;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    float l = s_red[a][0], h = s_red[3 + a][0];
-    for (int w = 1; w < kCsThreads / 64; ++w) {
-      l = __builtin_fminf(l, s_red[a][w]);
-      h = __builtin_fmaxf(h, s_red[3 + a][w]);
-    }
-    lo[a] = l;
-    ext = __builtin_fmaxf(ext, h - l);
-  }
-  if (!(ext > 0.f) || !(ext < 3.0e38f)) ext = 1.f;
-  const float invh = 16.f / ext;
-  auto cell_of = [&](float x, float y, float z) {
-    // clamped as floats: 0 * inf (a subnormal extent makes invh = +inf), a NaN
-    // or an infinite coordinate must not reach the float -> int conversion
-    const int ix = (int)__builtin_fminf(__builtin_fmaxf((x - lo[0]) * invh, 0.f), 15.f);
-    const int iy = (int)__builtin_fminf(__builtin_fmaxf((y - lo[1]) * invh, 0.f), 15.f);
-    const int iz = (int)__builtin_fminf(__builtin_fmaxf((z - lo[2]) * invh, 0.f), 15.f);
-    return cs_spread4(ix) | (cs_spread4(iy) << 1) | (cs_spread4(iz) << 2);
-  };
-  for (int k = t; k < cnt; k += kCsThreads)
-    atomicAdd(&s_cnt[cell_of(in[k * 3 + 0], in[k * 3 + 1], in[k * 3 + 2])], 1);
-  __syncthreads();
-  {  // exclusive prefix sum over 4096 cells, 4 per thread
-    int v[4], sum = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      v[i] = s_cnt[4 * t + i];
-      sum += v[i];
-    }
-    int incl = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int o = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += o;
-    }
-    if (lane == 63) s_wsum[wave] = incl;
-    __syncthreads();
-    int base = incl - sum;
-    for (int w = 0; w < wave; ++w) base += s_wsum[w];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      s_start[4 * t + i] = base;
-      base += v[i];
-    }
-    __syncthreads();
-    for (int c = t; c < kCsCells; c += kCsThreads) s_cnt[c] = 0;
-    __syncthreads();
-  }
-  for (int k = t; k < cnt; k += kCsThreads) {
-    const float x = in[k * 3 + 0], y = in[k * 3 + 1], z = in[k * 3 + 2];
-    const int c = cell_of(x, y, z);
-    out.pts[s_start[c] + atomicAdd(&s_cnt[c], 1)] = make_float4(x, y, z, __int_as_float(k));
-  }
-  for (int k = cnt + t; k < cp; k += kCsThreads)
-    out.pts[k] = make_float4(__builtin_inff(), __builtin_inff(), __builtin_inff(), __int_as_float(kCsPad));
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  for (int tl = t; tl < cp / kCsTile; tl += kCsThreads) {
-    float bl[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
-    float bh[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-    for (int i = 0; i < kCsTile; ++i) {
-      const float4 p = out.pts[tl * kCsTile + i];
-      if (__float_as_int(p.w) != kCsPad) {
-        bl[0] = __builtin_fminf(bl[0], p.x); bh[0] = __builtin_fmaxf(bh[0], p.x);
-        bl[1] = __builtin_fminf(bl[1], p.y); bh[1] = __builtin_fmaxf(bh[1], p.y);
-        bl[2] = __builtin_fminf(bl[2], p.z); bh[2] = __builtin_fmaxf(bh[2], p.z);
-      }
-    }
-    out.tbox[2 * tl + 0] = make_float4(bl[0], bl[1], bl[2], 0.f);
-    out.tbox[2 * tl + 1] = make_float4(bh[0], bh[1], bh[2], 0.f);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  for (int bt = t; bt < cp / kCsBatch; bt += kCsThreads) {
-    float bl[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
-    float bh[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-    for (int i = 0; i < kCsBatch / kCsTile; ++i) {
-      const float4 l = out.tbox[2 * (bt * (kCsBatch / kCsTile) + i) + 0];
-      const float4 h = out.tbox[2 * (bt * (kCsBatch / kCsTile) + i) + 1];
-      bl[0] = __builtin_fminf(bl[0], l.x); bh[0] = __builtin_fmaxf(bh[0], h.x);
-      bl[1] = __builtin_fminf(bl[1], l.y); bh[1] = __builtin_fmaxf(bh[1], h.y);
-      bl[2] = __builtin_fminf(bl[2], l.z); bh[2] = __builtin_fmaxf(bh[2], h.z);
-    }
-    out.bbox[2 * bt + 0] = make_float4(bl[0], bl[1], bl[2], 0.f);
-    out.bbox[2 * bt + 1] = make_float4(bh[0], bh[1], bh[2], 0.f);
-  }
-}
-
-template <int Q>
+// B*N*M pairs never evaluated.  Both sides are Morton-sorted with boxes per
+// tile and per batch (cs_sort.h: the index, the frame of a pruned search and
+// why the box tests are exact).  nm_distance_sorted_kernel keeps the
+// brute-force skeleton -- a lane owns a query, candidates stream through LDS
+// batches -- and skips a tile / batch when the distance between the box of the
+// wave's 64 queries and the tile's box already exceeds the worst current best
+// of the wave.  Ties go to the lowest ORIGINAL index (chamfer3D.cu:36,46,126)
+// by minimising the key {distance bits, original index} -- the visiting order
+// no longer is the index order.
 __global__ __launch_bounds__(kCdThreads) void nm_distance_sorted_kernel(
     int n1, int n2, char *__restrict__ scratch, float *__restrict__ dist1,
     float *__restrict__ dist2, int *__restrict__ idx1, int *__restrict__ idx2) {
   const int dir = blockIdx.z;
   const int nq = dir == 0 ? n1 : n2;
   const int nc = dir == 0 ? n2 : n1;
-  if ((int)blockIdx.x * (kCdThreads * Q) >= nq) return;
+  if ((int)blockIdx.x * kCdThreads >= nq) return;
   const int cloud = blockIdx.y;
   const long long per_cloud = cs_side_bytes(n1) + cs_side_bytes(n2);
   char *cbase = scratch + (size_t)cloud * per_cloud;
@@ -327,40 +176,25 @@ __global__ __launch_bounds__(kCdThreads) void nm_distance_sorted_kernel(
   __shared__ __attribute__((aligned(16))) float4 tbx[2 * kCsBatch / kCsTile];
 
   const int tid = threadIdx.x;
-  float qx[Q], qy[Q], qz[Q];
-  int qorig[Q];
-  unsigned long long best[Q];
-  float qlo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
-  float qhi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-#pragma unroll
-  for (int q = 0; q < Q; ++q) {
-    // a wave's 64*Q queries are consecutive in the sorted order (a compact box)
-    int j = blockIdx.x * (kCdThreads * Q) + (tid >> 6) * (64 * Q) + q * 64 + (tid & 63);
-    const bool valid = j < nq;
-    j = valid ? j : nq - 1;
-    const float4 p = qs.pts[j];
-    qx[q] = p.x; qy[q] = p.y; qz[q] = p.z;
-    qorig[q] = valid ? __float_as_int(p.w) : -1;
-    best[q] = ~0ull;
-    qlo[0] = __builtin_fminf(qlo[0], p.x); qhi[0] = __builtin_fmaxf(qhi[0], p.x);
-    qlo[1] = __builtin_fminf(qlo[1], p.y); qhi[1] = __builtin_fmaxf(qhi[1], p.y);
-    qlo[2] = __builtin_fminf(qlo[2], p.z); qhi[2] = __builtin_fmaxf(qhi[2], p.z);
-  }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {  // the wave's query box
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      qlo[a] = __builtin_fminf(qlo[a], __shfl_xor(qlo[a], off, 64));
-      qhi[a] = __builtin_fmaxf(qhi[a], __shfl_xor(qhi[a], off, 64));
-    }
-  }
+  // a wave's 64 queries are consecutive in the sorted order (a compact box)
+  int j = blockIdx.x * kCdThreads + tid;
+  const bool valid = j < nq;
+  j = valid ? j : nq - 1;
+  const float4 qp = qs.pts[j];
+  const float qx = qp.x, qy = qp.y, qz = qp.z;
+  const int qorig = valid ? __float_as_int(qp.w) : -1;
+  unsigned long long best = ~0ull;
+  const float inf = __builtin_inff();
+  float qlo[3] = {__builtin_fminf(inf, qx), __builtin_fminf(inf, qy), __builtin_fminf(inf, qz)};  // (a NaN stays out of the box)
+  float qhi[3] = {__builtin_fmaxf(-inf, qx), __builtin_fmaxf(-inf, qy), __builtin_fmaxf(-inf, qz)};
+  wave_box(qlo, qhi);
   float wmax = __builtin_inff();  // worst current best distance in this wave
 
   const int nb = (int)(cs_round_up(nc) / kCsBatch);
-  const int nblk = (nq + kCdThreads * Q - 1) / (kCdThreads * Q);
+  const int nblk = (nq + kCdThreads - 1) / kCdThreads;
   const int b0 = (int)((long long)blockIdx.x * nb / nblk);  // same relative position in the order
   for (int k = 0; k < 2 * nb; ++k) {
-    const int bi = b0 + ((k & 1) ? (k + 1) / 2 : -(k / 2));  // b0, b0+1, b0-1, b0+2, ...
+    const int bi = cs_batch_at(b0, k);
     if (bi < 0 || bi >= nb) continue;                        // block-uniform
     const bool need = !(cs_box_dist(qlo, qhi, cs.bbox[2 * bi], cs.bbox[2 * bi + 1]) > wmax);  // wave-uniform
     if (!__syncthreads_or(need)) continue;
@@ -382,60 +216,40 @@ __global__ __launch_bounds__(kCdThreads) void nm_distance_sorted_kernel(
         unsigned long long &from = near ? near : todo;
         const int s = __builtin_ctzll(from);
         from &= from - 1;
-        if (__int_as_float(__builtin_amdgcn_readlane(__float_as_int(lbl), s)) > wmax) continue;
-        {
-          // precise test: does ANY query of the wave still need this tile?  (the
-          // same monotone arithmetic on the gaps between the query POINT and
-          // the tile's box, against that query's own best)
-          const float4 tlo = tbx[2 * s], thi = tbx[2 * s + 1];
-          bool mine = false;
-#pragma unroll
-          for (int q = 0; q < Q; ++q) {
-            const float gx = __builtin_fmaxf(__builtin_fmaxf(tlo.x - qx[q], qx[q] - thi.x), 0.f);
-            const float gy = __builtin_fmaxf(__builtin_fmaxf(tlo.y - qy[q], qy[q] - thi.y), 0.f);
-            const float gz = __builtin_fmaxf(__builtin_fmaxf(tlo.z - qz[q], qz[q] - thi.z), 0.f);
-            mine |= !(sqdist3(gx, gy, gz) > __uint_as_float((unsigned)(best[q] >> 32)));
-          }
-          if (!__any(mine)) continue;
-        }
+        if (read_lane(lbl, s) > wmax) continue;
+        // precise test: does ANY query of the wave still need this tile?  (the query POINT against the tile's box
+        // and that query's own best)
+        const float mybest = __uint_as_float((unsigned)(best >> 32));
+        if (!__any(!(cs_point_box_dist(qx, qy, qz, tbx[2 * s], tbx[2 * s + 1]) > mybest))) continue;
 #pragma unroll
         for (int c = 0; c < kCsTile; ++c) {
           const float4 p = tile[s * kCsTile + c];
-          const unsigned lo32 = __float_as_uint(p.w);
-#pragma unroll
-          for (int q = 0; q < Q; ++q) {
-            const float d = sqdist3(p.x - qx[q], p.y - qy[q], p.z - qz[q]);
-            const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | lo32;
-            best[q] = key < best[q] ? key : best[q];
-          }
+          const float d = sqdist3(p.x - qx, p.y - qy, p.z - qz);
+          const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | __float_as_uint(p.w);
+          best = key < best ? key : best;
         }
-        float m = __uint_as_float((unsigned)(best[0] >> 32));
-#pragma unroll
-        for (int q = 1; q < Q; ++q) m = __builtin_fmaxf(m, __uint_as_float((unsigned)(best[q] >> 32)));
-        wmax = cs_wave_max(m);
+        wmax = wave_max(__uint_as_float((unsigned)(best >> 32)));
       }
     }
     __syncthreads();
   }
-#pragma unroll
-  for (int q = 0; q < Q; ++q) {
-    if (qorig[q] >= 0) {
-      // NaN bits sort above +inf, so a NaN key is the minimum only when every
-      // distance of the query is NaN; a padding entry (+inf coordinates) is the
-      // minimum only when every real candidate's distance is: both are the
-      // "all NaN" query of the contract, written as (NaN, 0) like the
-      // exhaustive kernel does.
-      unsigned dbits = (unsigned)(best[q] >> 32);
-      int bi = (int)(unsigned)best[q];
-      if (dbits > kCdInfBits || bi == kCsPad) {
-        dbits = kCdNanBits;
-        bi = 0;
-      }
-      result[qorig[q]] = __uint_as_float(dbits);
-      result_i[qorig[q]] = bi;
+  if (qorig >= 0) {
+    // NaN bits sort above +inf, so a NaN key is the minimum only when every
+    // distance of the query is NaN; a padding entry (+inf coordinates) is the
+    // minimum only when every real candidate's distance is: both are the
+    // "all NaN" query of the contract, written as (NaN, 0) like the
+    // exhaustive kernel does.
+    unsigned dbits = (unsigned)(best >> 32);
+    int bi = (int)(unsigned)best;
+    if (dbits > kCdInfBits || bi == kCsPad) {
+      dbits = kCdNanBits;
+      bi = 0;
     }
+    result[qorig] = __uint_as_float(dbits);
+    result_i[qorig] = bi;
   }
 }
+
 
 // Gradient.  One thread per (cloud, point); both directions in one launch.
 // grad_xyzA[j] += 2 g (a_j - b_idx), grad_xyzB[idx] -= same (float atomics,
@@ -558,12 +372,6 @@ extern "C" int mvp_chamfer_forward(int b, int n, int m, const float *xyz1,
   return check_launch("mvp_chamfer_forward");
 }
 
-namespace mvp {
-void cs_sort_launch(int b, int n1, int n2, const float *xyz1, const float *xyz2, char *scratch, hipStream_t stream) {
-  hipLaunchKernelGGL(chamfer_sort_kernel, dim3(2, b), dim3(kCsThreads), 0, stream, n1, n2, xyz1, xyz2, scratch);
-}
-}  // namespace mvp
-
 extern "C" long long mvp_chamfer_scratch_bytes(int b, int n, int m) {
   if (b < 0 || n < 0 || m < 0) return -1;
   return (long long)b * (cs_side_bytes(n) + cs_side_bytes(m));
@@ -587,7 +395,7 @@ extern "C" int mvp_chamfer_forward_sorted(int b, int n, int m, const float *xyz1
   // 0.88 / 1.02 / 1.35 ms at (64, 16384, 16384); exhaustive 3.95 ms).
   const int big = n > m ? n : m;
   dim3 grid((big + kCdThreads - 1) / kCdThreads, b, 2);
-  hipLaunchKernelGGL(nm_distance_sorted_kernel<1>, grid, dim3(kCdThreads), 0, as_stream(stream), n, m,
+  hipLaunchKernelGGL(nm_distance_sorted_kernel, grid, dim3(kCdThreads), 0, as_stream(stream), n, m,
                      reinterpret_cast<char *>(scratch), dist1, dist2, idx1, idx2);
   return check_launch("mvp_chamfer_forward_sorted");
 }

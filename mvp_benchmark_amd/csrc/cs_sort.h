@@ -1,9 +1,29 @@
-// Morton-sorted point sets with bounding boxes per 16 ("tile") and per 1024 ("batch") sorted points: the
-// index behind the pruned exact searches (chamfer.hip: nearest neighbour; pn2_query.hip: k nearest).
-// chamfer_sort_kernel (chamfer.hip) writes it into caller-provided scratch; see there for the exactness
-// argument of the box tests.
+// The Morton index: a cloud's points in the order of 16^3 cells, with bounding boxes over runs of that order.  It is
+// behind the three pruned exact searches -- chamfer.hip (nearest neighbour), pn2_query.hip (k nearest), fps.hip
+// (furthest point sampling) -- and is built by cs_sort.hip into caller-provided scratch.
+//
+// Cells and order.  The cloud's bounding box [lo, lo + ext]^3 (ext = its largest extent; 1 when that is 0, subnormal-
+// small, infinite or NaN) is cut into 16 x 16 x 16 cells, a point's cell per axis is (int)clamp((x - lo) * (16 / ext),
+// 0, 15) -- NaN lands in cell 0, +-inf in 0 / 15 -- and cells are numbered by interleaving the three 4-bit indices
+// (x in bits 0, 3, 6, 9).  One workgroup sorts one cloud by cell with a counting sort in LDS.  The order INSIDE a cell
+// is whatever the LDS atomics gave: it differs from run to run, and no consumer may depend on it.
+// An entry is float4 {x, y, z, bits(original index)}, the coordinates bitwise the input's.
+//
+// Layout, two conventions:
+//   * a "side" (Chamfer, kNN; struct CsSide): cs_round_up(c) entries, the padding {+inf, +inf, +inf, kCsPad}; then the
+//     box {lo, hi} (two float4, .w = 0) of every "tile" of 16 consecutive entries; then of every "batch" of 1024.
+//     Padding is in no box; a tile of padding only has the empty box {+inf, -inf}.  A cloud pair's two sides follow
+//     each other: cs_side_bytes(n1) + cs_side_bytes(n2) bytes per cloud.
+//   * points only (FPS): npad entries per cloud, the padding {0, 0, 0, -1}; no boxes (fps_sorted_kernel keeps one box
+//     per lane in registers).
+//
+// Exactness of the box tests.  cs_box_dist / cs_point_box_dist run sqdist3's subtract / fma chain on per-axis gaps
+// that are <= every member pair's |difference|; float subtract, multiply and fma are monotone, so the box distance
+// never exceeds a member pair's computed distance.  A search skips a box only on strict `>` against its current bound:
+// a candidate that EQUALS the bound is still evaluated, and the result is the exhaustive search's.
 #pragma once
 #include "common.h"
+#include "wave.h"
 
 namespace mvp {
 
@@ -11,7 +31,7 @@ constexpr int kCsThreads = 1024;
 constexpr int kCsCells = 4096;  // 16^3
 constexpr int kCsTile = 16;
 constexpr int kCsBatch = 1024;
-constexpr int kCsPad = 0x7fffffff;  // original index of a padding entry
+constexpr int kCsPad = 0x7fffffff;  // original index of a side's padding entry
 
 __host__ __device__ inline long long cs_round_up(long long c) { return (c + kCsBatch - 1) / kCsBatch * kCsBatch; }
 // bytes of one sorted side holding c points: points + tile boxes + batch boxes
@@ -21,7 +41,7 @@ __host__ __device__ inline long long cs_side_bytes(long long c) {
 }
 
 struct CsSide {
-  float4 *pts;   // cp sorted points (padding: +inf coordinates, index kCsPad)
+  float4 *pts;   // cp sorted points
   float4 *tbox;  // 2 per tile: lo, hi
   float4 *bbox;  // 2 per batch: lo, hi
 };
@@ -34,8 +54,10 @@ __host__ __device__ inline CsSide cs_carve(char *base, long long c) {
   return s;
 }
 
-// squared distance between two axis-aligned boxes (0 if they overlap), with
-// the rounding behaviour described above
+// ---- the frame of a pruned search over a side (a lane owns a query, a wave's 64 consecutive sorted queries sit in a
+// small box -- wave_box of wave.h --, candidates stream through LDS one batch at a time)
+
+// squared distance between two axis-aligned boxes (0 if they overlap)
 __device__ __forceinline__ float cs_box_dist(const float (&qlo)[3], const float (&qhi)[3],
                                              const float4 &tlo, const float4 &thi) {
   const float gx = __builtin_fmaxf(__builtin_fmaxf(tlo.x - qhi[0], qlo[0] - thi.x), 0.f);
@@ -43,25 +65,21 @@ __device__ __forceinline__ float cs_box_dist(const float (&qlo)[3], const float 
   const float gz = __builtin_fmaxf(__builtin_fmaxf(tlo.z - qhi[2], qlo[2] - thi.z), 0.f);
   return sqdist3(gx, gy, gz);
 }
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float cs_dpp_max(float v) {
-  const float o = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, ROW_MASK, 0xF, false));
-  return __builtin_fmaxf(v, o);
+// the same between a point and a box
+__device__ __forceinline__ float cs_point_box_dist(float x, float y, float z, const float4 &tlo, const float4 &thi) {
+  const float gx = __builtin_fmaxf(__builtin_fmaxf(tlo.x - x, x - thi.x), 0.f);
+  const float gy = __builtin_fmaxf(__builtin_fmaxf(tlo.y - y, y - thi.y), 0.f);
+  const float gz = __builtin_fmaxf(__builtin_fmaxf(tlo.z - z, z - thi.z), 0.f);
+  return sqdist3(gx, gy, gz);
 }
-// wave64 maximum with DPP row operations only; result taken from lane 63
-__device__ __forceinline__ float cs_wave_max(float v) {
-  v = cs_dpp_max<0xB1, 0xF>(v);   // quad_perm [1,0,3,2]
-  v = cs_dpp_max<0x4E, 0xF>(v);   // quad_perm [2,3,0,1]
-  v = cs_dpp_max<0x141, 0xF>(v);  // row_half_mirror
-  v = cs_dpp_max<0x140, 0xF>(v);  // row_mirror
-  v = cs_dpp_max<0x142, 0xA>(v);  // row_bcast15 -> rows 1, 3
-  v = cs_dpp_max<0x143, 0xC>(v);  // row_bcast31 -> rows 2, 3
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
+// k-th batch of the outward order b0, b0+1, b0-1, b0+2, ... (b0: the query block's own relative position in the
+// candidates' order, so the bounds are tight after the first batch or two); may fall outside [0, nb)
+__device__ __forceinline__ int cs_batch_at(int b0, int k) { return b0 + ((k & 1) ? (k + 1) / 2 : -(k / 2)); }
 
-// Sorts both sides of every cloud pair: xyz1 (b, n1, 3) -> side 0, xyz2 (b, n2, 3) -> side 1 of the cloud's
-// scratch area (cs_side_bytes(n1) + cs_side_bytes(n2) bytes per cloud).  chamfer.hip.
+// Sorts both sides of every cloud pair: xyz1 (b, n1, 3) -> side 0, xyz2 (b, n2, 3) -> side 1 of the cloud's scratch
+// area.
 void cs_sort_launch(int b, int n1, int n2, const float *xyz1, const float *xyz2, char *scratch, hipStream_t stream);
+// Sorts every cloud of xyz (b, n, 3) into `sorted` (b, npad), points only.
+void cs_sort_points_launch(int b, int n, int npad, const float *xyz, float4 *sorted, hipStream_t stream);
 
 }  // namespace mvp

@@ -39,6 +39,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "cs_sort.h"
 
 namespace mvp {
 
@@ -51,30 +52,6 @@ __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_s_barrier();
 }
 
-// Unsigned 32-bit max with one DPP-modified operand: a single v_max_u32 per
-// step (lanes a row mask leaves unwritten combine with 0, the identity).
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ unsigned dpp_umax32(unsigned v) {
-  const unsigned o = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, false);
-  return o > v ? o : v;
-}
-__device__ __forceinline__ unsigned wave_umax32(unsigned v) {
-  v = dpp_umax32<0xB1, 0xF>(v);   // quad_perm [1,0,3,2]
-  v = dpp_umax32<0x4E, 0xF>(v);   // quad_perm [2,3,0,1]
-  v = dpp_umax32<0x141, 0xF>(v);  // row_half_mirror
-  v = dpp_umax32<0x140, 0xF>(v);  // row_mirror
-  v = dpp_umax32<0x142, 0xA>(v);  // row_bcast15 -> rows 1, 3
-  v = dpp_umax32<0x143, 0xC>(v);  // row_bcast31 -> rows 2, 3
-  return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-__device__ __forceinline__ unsigned row16_umax32(unsigned v) {  // butterfly: every lane of the row gets the max
-  v = dpp_umax32<0xB1, 0xF>(v);
-  v = dpp_umax32<0x4E, 0xF>(v);
-  v = dpp_umax32<0x141, 0xF>(v);
-  v = dpp_umax32<0x140, 0xF>(v);
-  return v;
-}
-
 // Wave64 max of a u64 key {value bits, tie word}, returned wave-uniform.  A
 // 64-bit compare-and-select costs five dependent instructions per DPP step;
 // the lexicographic max is instead taken as two 32-bit reductions -- the value,
@@ -83,26 +60,26 @@ __device__ __forceinline__ unsigned row16_umax32(unsigned v) {  // butterfly: ev
 // tie word is fetched with one v_readlane instead of a second DPP reduction.
 __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
   const unsigned hi = (unsigned)(v >> 32), lo = (unsigned)v;
-  const unsigned mh = wave_umax32(hi);
+  const unsigned mh = wave_max(hi);
   const unsigned long long holders = __ballot(hi == mh);  // never empty
   unsigned ml;
   if ((holders & (holders - 1ull)) == 0ull)  // wave-uniform
     ml = (unsigned)__builtin_amdgcn_readlane((int)lo, __builtin_ctzll(holders));
   else
-    ml = wave_umax32(hi == mh ? lo : 0u);
+    ml = wave_max(hi == mh ? lo : 0u);
   return ((unsigned long long)mh << 32) | ml;
 }
 // The same over the 16 lanes of row 0 (valid in every lane of that row; taken
 // from lane 0).
 __device__ __forceinline__ unsigned long long row16_max_u64(unsigned long long v) {
   const unsigned hi = (unsigned)(v >> 32), lo = (unsigned)v;
-  const unsigned mh = (unsigned)__builtin_amdgcn_readfirstlane((int)row16_umax32(hi));
+  const unsigned mh = (unsigned)__builtin_amdgcn_readfirstlane((int)row16_max(hi));
   const unsigned long long holders = __ballot(hi == mh) & 0xFFFFull;  // row 0 only; never empty
   unsigned ml;
   if ((holders & (holders - 1ull)) == 0ull)
     ml = (unsigned)__builtin_amdgcn_readlane((int)lo, __builtin_ctzll(holders));
   else
-    ml = (unsigned)__builtin_amdgcn_readfirstlane((int)row16_umax32(hi == mh ? lo : 0u));
+    ml = (unsigned)__builtin_amdgcn_readfirstlane((int)row16_max(hi == mh ? lo : 0u));
   return ((unsigned long long)mh << 32) | ml;
 }
 
@@ -161,14 +138,14 @@ __device__ __forceinline__ void pick_point(const float (&px)[P], const float (&p
 // wave_max_u64 that also reports whether more than one lane holds the maximal VALUE (high word)
 __device__ __forceinline__ unsigned long long wave_max_u64_dup(unsigned long long v, bool &several) {
   const unsigned hi = (unsigned)(v >> 32), lo = (unsigned)v;
-  const unsigned mh = wave_umax32(hi);
+  const unsigned mh = wave_max(hi);
   const unsigned long long holders = __ballot(hi == mh);  // never empty
   several = (holders & (holders - 1ull)) != 0ull;
   unsigned ml;
   if (!several)  // wave-uniform
     ml = (unsigned)__builtin_amdgcn_readlane((int)lo, __builtin_ctzll(holders));
   else
-    ml = wave_umax32(hi == mh ? lo : 0u);
+    ml = wave_max(hi == mh ? lo : 0u);
   return ((unsigned long long)mh << 32) | ml;
 }
 
@@ -355,15 +332,12 @@ __global__ __launch_bounds__(1024) void fps_kernel(
 // where every lane owns up to 16 points and a round costs 8 instructions per
 // point for the distance update alone).
 //
-// fps_sort_kernel buckets the cloud into 16^3 Morton-ordered cells (counting
-// sort in LDS) and writes {x, y, z, bits(original index)} in that order into
-// caller scratch.  fps_sorted_kernel gives every lane P CONSECUTIVE sorted
-// points -- a small box -- and skips the update of a whole wave when the new
-// sample is, for each of its lanes, farther from the lane's box than the
-// lane's largest running minimum (no point can change: min(temp, d) = temp;
-// the box distance uses the monotone subtract/fma chain of sqdist3 on per-axis
-// gaps, so it never exceeds a member's computed distance).  After ~100 samples
-// 15-35 % of the waves still update.
+// The cloud is Morton-sorted into caller scratch (cs_sort.h: the index, points
+// only, and why box tests are exact).  fps_sorted_kernel gives every lane P
+// CONSECUTIVE sorted points -- a small box -- and skips the update of a whole
+// wave when the new sample is, for each of its lanes, farther from the lane's
+// box than the lane's largest running minimum (no point can change:
+// min(temp, d) = temp).  After ~100 samples 15-35 % of the waves still update.
 // Lanes are no longer the reference's threads, so the arg-max key cannot carry
 // the reference's tie order.  The reduction finds the maximum and one holder;
 // a round in which the maximum is attained more than once (inside the holder's
@@ -371,103 +345,6 @@ __global__ __launch_bounds__(1024) void fps_kernel(
 // detected with one compare + ballot and resolved exactly from the ORIGINAL
 // indices -- smallest bit-reversed slot k % BS, then smallest k
 // (furthest_point_sample_cuda.cu:17-23,69-70) -- out of line, through LDS.
-constexpr int kFsCells = 4096;
-
-__global__ __launch_bounds__(1024) void fps_sort_kernel(int n, int npad, const float *__restrict__ xyz,
-                                                        float4 *__restrict__ sorted) {
-  const int cloud = blockIdx.x;
-  const float *__restrict__ in = xyz + (size_t)cloud * n * 3;
-  float4 *__restrict__ out = sorted + (size_t)cloud * npad;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  __shared__ int s_cnt[kFsCells];
-  __shared__ int s_start[kFsCells];
-  __shared__ float s_red[6][16];
-  __shared__ int s_wsum[16];
-  float mn[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
-  float mx[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-  for (int k = t; k < n; k += 1024) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const float v = in[k * 3 + a];
-      mn[a] = __builtin_fminf(mn[a], v);
-      mx[a] = __builtin_fmaxf(mx[a], v);
-    }
-  }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      mn[a] = __builtin_fminf(mn[a], __shfl_xor(mn[a], off, 64));
-      mx[a] = __builtin_fmaxf(mx[a], __shfl_xor(mx[a], off, 64));
-    }
-    if (lane == 0) {
-      s_red[a][wave] = mn[a];
-      s_red[3 + a][wave] = mx[a];
-    }
-  }
-  for (int c = t; c < kFsCells; c += 1024) s_cnt[c] = 0;
-  __syncthreads();
-  float lo[3], ext = 0.f;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    float l = s_red[a][0], h = s_red[3 + a][0];
-    for (int w = 1; w < 16; ++w) {
-      l = __builtin_fminf(l, s_red[a][w]);
-      h = __builtin_fmaxf(h, s_red[3 + a][w]);
-    }
-    lo[a] = l;
-    ext = __builtin_fmaxf(ext, h - l);
-  }
-  if (!(ext > 0.f) || !(ext < 3.0e38f)) ext = 1.f;
-  const float invh = 16.f / ext;
-  auto spread4 = [](int v) {  // bit i -> bit 3i
-    v &= 0xF;
-    v = (v | (v << 4)) & 0xC3;
-    v = (v | (v << 2)) & 0x249;
-    return v;
-  };
-  auto cell_of = [&](float x, float y, float z) {
-    // clamped as floats: 0 * inf (a subnormal extent makes invh = +inf) must not reach the float -> int conversion
-    const int ix = (int)__builtin_fminf(__builtin_fmaxf((x - lo[0]) * invh, 0.f), 15.f);
-    const int iy = (int)__builtin_fminf(__builtin_fmaxf((y - lo[1]) * invh, 0.f), 15.f);
-    const int iz = (int)__builtin_fminf(__builtin_fmaxf((z - lo[2]) * invh, 0.f), 15.f);
-    return spread4(ix) | (spread4(iy) << 1) | (spread4(iz) << 2);
-  };
-  for (int k = t; k < n; k += 1024) atomicAdd(&s_cnt[cell_of(in[k * 3 + 0], in[k * 3 + 1], in[k * 3 + 2])], 1);
-  __syncthreads();
-  {
-    int v[4], sum = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      v[i] = s_cnt[4 * t + i];
-      sum += v[i];
-    }
-    int incl = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int o = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += o;
-    }
-    if (lane == 63) s_wsum[wave] = incl;
-    __syncthreads();
-    int base = incl - sum;
-    for (int w = 0; w < wave; ++w) base += s_wsum[w];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      s_start[4 * t + i] = base;
-      base += v[i];
-    }
-    __syncthreads();
-    for (int c = t; c < kFsCells; c += 1024) s_cnt[c] = 0;
-    __syncthreads();
-  }
-  for (int k = t; k < n; k += 1024) {
-    const float x = in[k * 3 + 0], y = in[k * 3 + 1], z = in[k * 3 + 2];
-    const int c = cell_of(x, y, z);
-    out[s_start[c] + atomicAdd(&s_cnt[c], 1)] = make_float4(x, y, z, __int_as_float(k));
-  }
-  for (int k = n + t; k < npad; k += 1024) out[k] = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
-}
 
 // Tie round, out of line: every lane has copied its running minima to s_pt; the
 // lanes that hold the maximum rank their points by the reference's order on the
@@ -595,7 +472,7 @@ __global__ __launch_bounds__(1024) void fps_sorted_kernel(int n, int m, const fl
     const unsigned long long kw = (lane & 15) < NW ? s_wkey[par][lane & 15] : 0ull;
     const float4 cw = s_wsel[par][(lane & 15) < NW ? (lane & 15) : 0];
     const unsigned hi = (unsigned)(kw >> 32);
-    const unsigned mh = (unsigned)__builtin_amdgcn_readfirstlane((int)row16_umax32(hi));
+    const unsigned mh = (unsigned)__builtin_amdgcn_readfirstlane((int)row16_max(hi));
     const unsigned long long hold = __ballot(hi == mh) & 0xFFFFull;   // row 0: one lane per wave of the block
     const int ww = (int)__builtin_ctzll(hold);
     const unsigned lo_w = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)kw, ww);
@@ -870,7 +747,7 @@ extern "C" int mvp_furthest_point_sampling_sorted(int b, int n, int m, const flo
   const int pp = p <= 6 ? 6 : p <= 8 ? 8 : p <= 12 ? 12 : 16;
   float4 *sorted = reinterpret_cast<float4 *>(scratch);
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(fps_sort_kernel, dim3(b), dim3(1024), 0, st, n, 1024 * pp, points, sorted);
+  cs_sort_points_launch(b, n, 1024 * pp, points, sorted, st);
 #define MVP_FPS_SORTED(PP) \
   hipLaunchKernelGGL((fps_sorted_kernel<PP>), dim3(b), dim3(1024), 0, st, n, m, points, sorted, temp, idx)
   if (pp == 6) MVP_FPS_SORTED(6);

@@ -239,12 +239,10 @@ __global__ __launch_bounds__(kFixWaves * 64) void knn_fix_kernel(
 }
 
 // Pruned exact variant for large clouds (n >= 4096, k <= 32): the same result with most of the m*n pairs
-// never evaluated.  Both point sets are Morton-sorted with boxes per 16 and per 1024 points (cs_sort.h,
-// chamfer_sort_kernel); a lane owns a query -- a wave's 64 consecutive sorted queries sit in a small box --
-// and keeps a max-heap of its k+1 best candidates in an LDS column; batches are visited outwards from the
-// query block's own position in the order, a batch / tile is skipped when its box is farther from the
-// wave's query box than the worst heap root of the wave, and a tile is evaluated only if some query's own
-// root still reaches its box (strict `>` on monotone box distances, as in the sorted Chamfer kernel).
+// never evaluated.  Both point sets are Morton-sorted with boxes per 16 and per 1024 points (cs_sort.h: the
+// index and the frame of the search); a lane owns a query and keeps an ascending list of its k+1 best
+// candidates; a batch / tile is skipped when its box is farther from the wave's query box than the worst list
+// tail of the wave, and a tile is evaluated only if some query's own tail still reaches its box.
 // Exactness.  The reference admits candidates in INDEX order by strict `<` against the heap root and ends
 // with a heap sort (knn_cuda.cu:80-90): when the k+1 smallest distances of a query are pairwise different,
 // the k nearest are a unique set and the heap sort returns them in ascending order whatever the order of
@@ -276,14 +274,7 @@ __global__ __launch_bounds__(T) void knn_sorted_kernel(
   const int qorig = valid ? __float_as_int(q.w) : -1;
   const float qx = q.x, qy = q.y, qz = q.z;
   float qlo[3] = {qx, qy, qz}, qhi[3] = {qx, qy, qz};
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {  // the wave's query box
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      qlo[a] = __builtin_fminf(qlo[a], __shfl_xor(qlo[a], off, 64));
-      qhi[a] = __builtin_fmaxf(qhi[a], __shfl_xor(qhi[a], off, 64));
-    }
-  }
+  wave_box(qlo, qhi);
   float dd[KL];
   int ii[KL];
 #pragma unroll
@@ -299,7 +290,7 @@ __global__ __launch_bounds__(T) void knn_sorted_kernel(
   // the tile at the wave's own relative position in the candidates' order
   const int own_tile = (int)(((long long)blockIdx.x * T + (t & ~63) + 32) * (long long)(cs_round_up(n) / kCsTile) / max(1, m));
   for (int k = 0; k < 2 * nb; ++k) {
-    const int bi = b0 + ((k & 1) ? (k + 1) / 2 : -(k / 2));  // b0, b0+1, b0-1, b0+2, ...
+    const int bi = cs_batch_at(b0, k);
     if (bi < 0 || bi >= nb) continue;                        // block-uniform
     const bool need = !(cs_box_dist(qlo, qhi, cs.bbox[2 * bi], cs.bbox[2 * bi + 1]) > wmax);  // wave-uniform
     if (!__syncthreads_or(need)) continue;
@@ -320,12 +311,8 @@ __global__ __launch_bounds__(T) void knn_sorted_kernel(
         else s = 63 - (int)__builtin_clzll(lo_part);
         up = !up;
         todo &= ~(1ull << s);
-        if (__int_as_float(__builtin_amdgcn_readlane(__float_as_int(lbl), s)) > wmax) continue;
-        const float4 tlo = tbx[2 * s], thi = tbx[2 * s + 1];
-        const float gx = __builtin_fmaxf(__builtin_fmaxf(tlo.x - qx, qx - thi.x), 0.f);
-        const float gy = __builtin_fmaxf(__builtin_fmaxf(tlo.y - qy, qy - thi.y), 0.f);
-        const float gz = __builtin_fmaxf(__builtin_fmaxf(tlo.z - qz, qz - thi.z), 0.f);
-        if (!__any(!(sqdist3(gx, gy, gz) > dd[KL - 1]))) continue;   // no query's list reaches this tile
+        if (read_lane(lbl, s) > wmax) continue;
+        if (!__any(!(cs_point_box_dist(qx, qy, qz, tbx[2 * s], tbx[2 * s + 1]) > dd[KL - 1]))) continue;   // no query's list reaches this tile
         // (every candidate that ANY lane admits runs the insertion for the whole wave; letting each lane take its
         // own next survivor -- max-over-lanes(survivors) insertions per tile -- was slower: 0.93 -> 2.09 ms, the
         // per-lane LDS gather and the loop around it cost more than the insertions they save)
@@ -349,7 +336,7 @@ __global__ __launch_bounds__(T) void knn_sorted_kernel(
             changed = true;
           }
         }
-        if (changed) wmax = cs_wave_max(dd[KL - 1]);   // (wave-uniform)
+        if (changed) wmax = wave_max(dd[KL - 1]);   // (wave-uniform)
       }
     }
     __syncthreads();

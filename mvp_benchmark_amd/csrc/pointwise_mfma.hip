@@ -31,6 +31,7 @@
 // MFMAs.  Workgroups are numbered so that the ones that share an activation tile run
 // back to back on ONE XCD (its L2 serves the re-reads).
 #include "common.h"
+#include "wave.h"
 
 namespace mvp {
 
@@ -208,13 +209,6 @@ __device__ __forceinline__ void pw_mma(f32x16 (&acc)[TM][TN], const float (&a)[T
       for (int n = 0; n < TN; ++n) acc[i][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][j], b[n][j], acc[i][n], 0, 0, 0);
 }
 
-// Unsigned max with one DPP-modified operand (lanes a row mask leaves unwritten combine with 0, the identity).
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ unsigned pw_dpp_umax(unsigned v) {
-  const unsigned o = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, false);
-  return o > v ? o : v;
-}
-
 // keys (see pointwise_mfma_kernel, ROWMAX) -> val[i] = the row's maximum, idx[i] = the first position that attains it
 __global__ void pointwise_rowmax_unpack_kernel(long long total, const unsigned long long *__restrict__ keys,
                                                float *__restrict__ val, int *__restrict__ idx) {
@@ -339,13 +333,8 @@ __global__ __launch_bounds__(kMmThreads) __attribute__((amdgpu_waves_per_eu(TM =
         }
         // maximum over the 32 lanes that share this row (lanes 0..31 / 32..63): DPP inside the rows of 16, row_bcast15
         // into rows 1 and 3, whose last lanes then hold it
-        unsigned m = hi;
-        m = pw_dpp_umax<0xB1, 0xF>(m);    // quad_perm [1,0,3,2]
-        m = pw_dpp_umax<0x4E, 0xF>(m);    // quad_perm [2,3,0,1]
-        m = pw_dpp_umax<0x141, 0xF>(m);   // row_half_mirror
-        m = pw_dpp_umax<0x140, 0xF>(m);   // row_mirror
-        m = pw_dpp_umax<0x142, 0xA>(m);   // row_bcast15 -> rows 1, 3
-        const unsigned m0h = (unsigned)__builtin_amdgcn_readlane((int)m, 31), m1h = (unsigned)__builtin_amdgcn_readlane((int)m, 63);
+        const unsigned m = half32_max(hi);
+        const unsigned m0h = read_lane(m, 31), m1h = read_lane(m, 63);
         const unsigned mh = lk ? m1h : m0h;
         if (hi != 0u && hi == mh && m0 + lr < M)
           atomicMax(keys + (m0 + lr), ((unsigned long long)hi << 32) | (unsigned long long)lo);
