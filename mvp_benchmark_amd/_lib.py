@@ -111,6 +111,8 @@ def load():
     lib.mvp_pointwise_wgrad_mfma_scratch_bytes.argtypes = [ctypes.c_int] * 5
     lib.mvp_pointwise_max_backward_scratch_bytes.restype = ctypes.c_longlong
     lib.mvp_pointwise_max_backward_scratch_bytes.argtypes = [ctypes.c_int] * 4
+    lib.mvp_share_gather_sum_lds_bytes.restype = ctypes.c_longlong
+    lib.mvp_share_gather_sum_lds_bytes.argtypes = [ctypes.c_int] * 2
     for name, sig in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype = ctypes.c_int

@@ -85,6 +85,23 @@ def test_guards_and_scratch_sizes_of_the_widened_entry_points():
     assert lib.mvp_share_weighted_sum(1, 8, 2, 4, 8, null, null, null, null) == -2
     assert lib.mvp_share_weighted_sum(0, 8, 2, 4, 8, null, null, null, null) == 0
     assert lib.mvp_share_weighted_sum_grad(1, 8, 2, 4, 8, null, null, null, null, null, null) == -2
+    # ... with the gather fused in: (b, share, cw, k, n_src, n); the `share` staged rows fit 96 KiB of LDS
+    gather = lambda *dims: lib.mvp_share_gather_sum(*dims, null, null, null, null, null)
+    gather_grad = lambda *dims: lib.mvp_share_gather_sum_grad(*dims, null, null, null, null, null, null, null)
+    for fn in (gather, gather_grad):
+        assert fn(1, 3, 2, 4, 8, 8) == -1                                # share
+        assert fn(1, 8, 2, 4, 0, 8) == -1 and fn(1, 8, 2, 4, -1, 8) == -1   # n_src <= 0
+        assert fn(0, 8, 2, 4, 0, 8) == -1                                # ... also in front of the empty batch
+        assert fn(1, 8, 2, 4, 8, -1) == -1 and fn(1, 8, 2, -1, 8, 8) == -1 and fn(65536, 8, 2, 4, 8, 8) == -1
+        for share in (1, 2, 4, 8, 16):
+            n_src = 24576 // share
+            assert lib.mvp_share_gather_sum_lds_bytes(share, n_src) == 96 * 1024
+            assert lib.mvp_share_gather_sum_lds_bytes(share, n_src + 1) == 96 * 1024 + 4 * share
+            assert fn(1, share, 2, 4, n_src, 65) == -2                   # covered: the null buffers are what is wrong
+            assert fn(1, share, 2, 4, n_src + 1, 65) == -1               # one row above the limit
+        assert fn(0, 8, 2, 4, 8, 8) == 0 and fn(1, 8, 0, 4, 8, 8) == 0 and fn(1, 8, 2, 4, 8, 0) == 0   # nothing to do
+    assert gather_grad(1, 8, 2, 0, 8, 8) == 0                            # k == 0: no gradient to write
+    assert gather(1, 8, 2, 0, 8, 8) == -2                                # ... but an output to zero
     # pointwise weight gradient: cout <= 64, positions a multiple of 4; one partial per run of 1024 positions
     assert _lib.pointwise_wgrad_scratch_bytes(2, 24, 24, 4096) == 2 * 4 * (24 * 24 + 24) * 4
     assert _lib.pointwise_wgrad_scratch_bytes(1, 24, 65, 4096) == 0
