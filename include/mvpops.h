@@ -43,7 +43,7 @@ extern "C" {
 #define MVP_ELAUNCH (-3)
 
 /* ABI version of this header; bumped on any signature change. */
-#define MVP_ABI_VERSION 19
+#define MVP_ABI_VERSION 20
 int mvp_abi_version(void);
 
 /* hipGetErrorString of the last launch failure seen on the calling thread
@@ -522,6 +522,33 @@ int mvp_pointwise_mfma_ex(int b, int cin, int cout, int len, const float *x,
                           const float *bias, int bias_per_cloud, const float *residual,
                           int flags, int group, float *y, int m_split, float *y2,
                           void *stream);
+
+/* ABI 20.  mvp_pointwise_mfma_ex (group = 1, one output) with the reduction split over workgroups: for a long reduction
+ * whose output has too few tiles to fill the chip (ECG's bottleneck layers, ecg.py: 1864 -> 768 at 256 points, 2824 /
+ * 1800 -> 1024 at 64 points).  Two launches: every workgroup reduces one chunk [s k_chunk, min((s + 1) k_chunk, cin)) of one
+ * output tile (x masked / rectified on load as in the plain call) and writes its raw accumulators to
+ * scratch[s][b][cout][len]; a second kernel adds the chunks and applies the epilogue.  No atomics: bit-reproducible.
+ *   mvp_pointwise_mfma_splitk_plan           the suggested k_chunk (a multiple of 16), or 0 = do not split.  Host-only and
+ *          pure (no GPU needed).  cin is the reduction length, cout the output rows: the data gradient asks with the two
+ *          swapped, as it calls.  Splits only cin > 512 with fewer than 512 output tiles (128 x 128; 64 rows for
+ *          cout <= 64, 64 columns for len <= 64): min(ceil(512 / tiles), cin / 128, 16) chunks, if that is >= 2.
+ *   mvp_pointwise_mfma_splitk_scratch_bytes  ceil(cin / k_chunk) * b * cout * len * 4, or 0 where the call would refuse the
+ *          shape or the chunk.
+ *   mvp_pointwise_mfma_splitk                the arguments of mvp_pointwise_mfma_ex without group, m_split and y2.
+ *          k_chunk not a positive multiple of 16: MVP_EBADARG; more than 32 chunks: MVP_EBADSHAPE; scratch NULL, not
+ *          16-byte aligned or smaller than the query's answer: MVP_EBADARG; every shape, flag and alignment refusal of
+ *          mvp_pointwise_mfma_ex unchanged.  k_chunk >= cin (one chunk) IS mvp_pointwise_mfma_ex; scratch may be NULL then.
+ * Arithmetic: chunk s is what mvp_pointwise_mfma_ex yields on the K-slice [s k_chunk, ...) of x (xmask) and w with the
+ * same prologue, no bias and no epilogue flags, bit for bit (a chunk is a whole number of the kernel's 16-wide slabs, so
+ * the order of every matrix instruction coincides); y is ((p0 + p1) + p2) + ... followed by + bias, ReLU, + residual (or
+ * the residual as a mask), ReLU as the flags say, each one IEEE float32 operation with the non-finite contract above. */
+int mvp_pointwise_mfma_splitk_plan(int b, int cin, int cout, int len);
+long long mvp_pointwise_mfma_splitk_scratch_bytes(int b, int cin, int cout, int len, int k_chunk);
+int mvp_pointwise_mfma_splitk(int b, int cin, int cout, int len, const float *x,
+                              const float *xmask, const float *w, int ldw, int w_kmajor,
+                              const float *bias, int bias_per_cloud, const float *residual,
+                              int flags, float *y, int k_chunk, void *scratch,
+                              long long scratch_bytes, void *stream);
 
 /* ABI 16.  (W x + bias) [then ReLU], reduced with max over ALL positions of a cloud inside the GEMM's epilogue
  * -- the PointNet stage of the completion networks: `x = self.conv4(x); global_feature, _ = torch.max(x, 2)`

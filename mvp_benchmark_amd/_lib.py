@@ -54,6 +54,7 @@ SIGNATURES = {
     "mvp_kabsch_svd3": "ipppppp",
     "mvp_pointwise_mfma": "iiiipppiippiip",
     "mvp_pointwise_mfma_ex": "iiiipppiipipiipip",
+    "mvp_pointwise_mfma_splitk": "iiiipppiipipipipq",
     "mvp_pointwise_wgrad_mfma": "iiiippppppq",
     "mvp_pointwise_wgrad_mfma_ex": "iiiipipppppq",
     "mvp_pointwise_max_backward": "iiiippppppppq",
@@ -65,7 +66,7 @@ SIGNATURES = {
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "f": ctypes.c_float,
        "q": ctypes.c_longlong}
 
-ABI_VERSION = 19  # MVP_ABI_VERSION of include/mvpops.h this binding was written against
+ABI_VERSION = 20  # MVP_ABI_VERSION of include/mvpops.h this binding was written against
 
 # default of mvp_emd_configure's `split` knob (csrc/emd.hip: emd_knobs)
 EMD_DEFAULT_SPLIT = 5
@@ -109,6 +110,10 @@ def load():
     lib.mvp_pointwise_wgrad_scratch_bytes.argtypes = [ctypes.c_int] * 4
     lib.mvp_pointwise_wgrad_mfma_scratch_bytes.restype = ctypes.c_longlong
     lib.mvp_pointwise_wgrad_mfma_scratch_bytes.argtypes = [ctypes.c_int] * 5
+    lib.mvp_pointwise_mfma_splitk_plan.restype = ctypes.c_int
+    lib.mvp_pointwise_mfma_splitk_plan.argtypes = [ctypes.c_int] * 4
+    lib.mvp_pointwise_mfma_splitk_scratch_bytes.restype = ctypes.c_longlong
+    lib.mvp_pointwise_mfma_splitk_scratch_bytes.argtypes = [ctypes.c_int] * 5
     lib.mvp_pointwise_max_backward_scratch_bytes.restype = ctypes.c_longlong
     lib.mvp_pointwise_max_backward_scratch_bytes.argtypes = [ctypes.c_int] * 4
     lib.mvp_share_gather_sum_lds_bytes.restype = ctypes.c_longlong
@@ -253,6 +258,16 @@ def pointwise_wgrad_mfma_scratch_bytes(b, cin, cout, length, with_bias):
     return int(load().mvp_pointwise_wgrad_mfma_scratch_bytes(int(b), int(cin), int(cout), int(length), int(with_bias)))
 
 
+def pointwise_mfma_splitk_plan(b, cin, cout, length):
+    """Suggested k_chunk of mvp_pointwise_mfma_splitk for a reduction of cin into cout rows (0: do not split).  No GPU needed."""
+    return int(load().mvp_pointwise_mfma_splitk_plan(int(b), int(cin), int(cout), int(length)))
+
+
+def pointwise_mfma_splitk_scratch_bytes(b, cin, cout, length, k_chunk):
+    """Scratch of mvp_pointwise_mfma_splitk (0: shape or chunk refused)."""
+    return int(load().mvp_pointwise_mfma_splitk_scratch_bytes(int(b), int(cin), int(cout), int(length), int(k_chunk)))
+
+
 def pointwise_max_backward_scratch_bytes(b, cin, cout, length):
     """Scratch of mvp_pointwise_max_backward's staged weight gradient (0: not covered, it gathers directly)."""
     return int(load().mvp_pointwise_max_backward_scratch_bytes(int(b), int(cin), int(cout), int(length)))
@@ -262,5 +277,6 @@ def exported_symbols():
     """All entry points include/mvpops.h declares."""
     return ["mvp_abi_version", "mvp_last_hip_error", "mvp_emd_scratch_bytes", "mvp_emd_configure", "mvp_chamfer_scratch_bytes", "mvp_knn_scratch_bytes", "mvp_fps_scratch_bytes", "mvp_fps_cluster_scratch_bytes",
             "mvp_scatter_scratch_bytes", "mvp_pointwise_wgrad_scratch_bytes", "mvp_pointwise_wgrad_mfma_scratch_bytes",
+            "mvp_pointwise_mfma_splitk_plan", "mvp_pointwise_mfma_splitk_scratch_bytes",
             "mvp_pointwise_max_backward_scratch_bytes", "mvp_share_gather_sum_lds_bytes"] \
         + list(SIGNATURES)

@@ -448,6 +448,148 @@ __global__ __launch_bounds__(kMmThreads) __attribute__((amdgpu_waves_per_eu(TM =
     }
 }
 
+// ------------------------------------------------------- forward / data gradient, split along K
+// A long reduction with too few output tiles to fill the chip (ECG's bottleneck layers: 1864 -> 768 at 256 points is 384
+// workgroups, 2824 -> 1024 at 64 points half-empty column tiles): the reduction is cut into `splits` chunks of k_chunk (a
+// multiple of BK, so a chunk's slabs -- and with them the order of every matrix instruction -- are those of the kernel
+// above run on that K-slice alone), a workgroup takes one (tile, chunk) and writes its raw accumulators to
+// partial[split][cloud][M][N]; pointwise_splitk_reduce_kernel adds the chunks in ascending order and applies the epilogue.
+// No atomics: the result is a fixed expression.  The prologues (xmask, ReLU of x) stay on load.  A kernel of its own, so
+// that the instances above compile to what they were.  TN = 1 (a 64-column tile) serves len <= 64.
+template <int TM, int TN, int BK, int AMODE, bool MASKED, bool XRELU>
+__global__ __launch_bounds__(kMmThreads) __attribute__((amdgpu_waves_per_eu(TM == 2 ? 3 : 5))) void pointwise_mfma_splitk_kernel(
+    int M, int N, int K, int nb, int k_chunk, int splits, const float *__restrict__ a, int a_ld, int a_vec,
+    const float *__restrict__ x, const float *__restrict__ xmask, float *__restrict__ partial) {
+  constexpr int BM = 64 * TM, BN = 64 * TN;
+  using IA = PwImg<BM, BK, AMODE>;
+  using IB = PwImg<BN, BK, kXC>;
+  static_assert(!(XRELU && MASKED), "ReLU of x on load and a mask on x are not combined");
+  __shared__ __attribute__((aligned(16))) float As[2][IA::floats];
+  __shared__ __attribute__((aligned(16))) float Bs[2][IB::floats];
+
+  const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
+  const long long tiles = (long long)tiles_m * tiles_n, total = tiles * splits * nb;
+  const long long work = pw_work_item(total);
+  if (work >= total) return;
+  const int m0 = (int)(work % tiles_m) * BM;               // the M tiles of one activation tile are neighbours
+  const int n0 = (int)((work / tiles_m) % tiles_n) * BN;
+  const int split = (int)((work / tiles) % splits);
+  const int cloud = (int)(work / (tiles * splits));
+  const int ks = split * k_chunk, ke = min(ks + k_chunk, K);   // this workgroup's share of the reduction
+
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int wm = wave >> 1, wn = wave & 1, lrow = lane & 31, lk = lane >> 5;
+  const float *xb = x + (size_t)cloud * K * N;
+  const float *mb = xmask ? xmask + (size_t)cloud * K * N : nullptr;
+  const size_t lda = a_ld;
+
+  f32x16 acc[TM][TN];
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  PwRegs<IA::vecs> ra;
+  PwRegs<IB::vecs> rb;
+  PwRegs<1> rnone;
+  PwRegs<MASKED ? IB::vecs : 1> rbm;
+  const int nk = (ke - ks + BK - 1) / BK;
+  pw_fetch<BM, BK, AMODE, false>(ra, rnone, a, nullptr, lda, m0, M, ks, ke, a_vec != 0, t);
+  pw_fetch<BN, BK, kXC, MASKED>(rb, rbm, xb, mb, N, n0, N, ks, ke, true, t);
+  pw_stash<BM, BK, AMODE, false>(As[0], ra, rnone, t);
+  pw_stash<BN, BK, kXC, MASKED, XRELU>(Bs[0], rb, rbm, t);
+  __syncthreads();
+  for (int s = 0; s < nk; ++s) {
+    const int buf = s & 1;
+    if (s + 1 < nk) {                                   // in flight while this slab computes
+      pw_fetch<BM, BK, AMODE, false>(ra, rnone, a, nullptr, lda, m0, M, ks + (s + 1) * BK, ke, a_vec != 0, t);
+      pw_fetch<BN, BK, kXC, MASKED>(rb, rbm, xb, mb, N, n0, N, ks + (s + 1) * BK, ke, true, t);
+    }
+#pragma unroll
+    for (int kg = 0; kg < BK / 8; ++kg) {
+      float av[TM][4], bv[TN][4];
+      pw_frag<TM, BM, BK, AMODE>(av, As[buf], wm * 32 * TM, kg, lrow, lk);
+      pw_frag<TN, BN, BK, kXC>(bv, Bs[buf], wn * 32 * TN, kg, lrow, lk);
+      pw_mma<TM, TN>(acc, av, bv);
+      if (kg == kPwStashAt(BK / 8, false) && s + 1 < nk) {
+        pw_stash<BM, BK, AMODE, false>(As[buf ^ 1], ra, rnone, t);
+        pw_stash<BN, BK, kXC, MASKED, XRELU>(Bs[buf ^ 1], rb, rbm, t);
+      }
+    }
+    if (s + 1 < nk) __syncthreads();
+  }
+
+  // partial[split][cloud][row][col]; C/D layout of 32x32: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+  float *pp = partial + ((size_t)split * nb + cloud) * M * N;
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      const int col = n0 + wn * 32 * TN + j * 32 + lrow;
+      const int row0 = m0 + wm * 32 * TM + i * 32 + 4 * lk;
+      float *pc = pp + (size_t)row0 * N + col;
+      if (col < N) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int dr = (r & 3) + 8 * (r >> 2);
+          if (dr < M - row0) pc[(size_t)dr * N] = acc[i][j][r];
+        }
+      }
+    }
+}
+
+// y = epilogue(partial[0] + partial[1] + ... in ascending order): one thread per four consecutive positions of one output
+// row (N % 4 == 0), every step one float32 operation -- + bias (bias_bs = M: one per cloud), ReLU, + residual or the
+// residual as a mask, ReLU again -- in the order of the kernel above.  The partials are read 16 bytes at a time (the
+// scratch is aligned); y and the residual too where the caller's pointers allow it (vec_io).
+__global__ __launch_bounds__(256) void pointwise_splitk_reduce_kernel(long long quads, int M, int N, int splits,
+                                                                      const float *__restrict__ partial,
+                                                                      const float *__restrict__ bias, int bias_bs,
+                                                                      const float *__restrict__ residual, int flags,
+                                                                      int vec_io, float *__restrict__ y) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= quads) return;
+  const bool relu = (flags & 1) != 0, relu_after = (flags & 2) != 0, res_is_mask = (flags & 4) != 0;
+  const size_t o = (size_t)e * 4, stride = (size_t)quads * 4;
+  const long long row = (long long)(o / (size_t)N);          // cloud * M + output channel
+  const int co = (int)(row % M), cloud = (int)(row / M);
+  float4 v = *reinterpret_cast<const float4 *>(partial + o);
+#pragma unroll 4
+  for (int s = 1; s < splits; ++s) {
+    const float4 q = *reinterpret_cast<const float4 *>(partial + (size_t)s * stride + o);
+    v.x += q.x;
+    v.y += q.y;
+    v.z += q.z;
+    v.w += q.w;
+  }
+  if (bias) {
+    const float bi = bias[(size_t)cloud * bias_bs + co];
+    v.x += bi;
+    v.y += bi;
+    v.z += bi;
+    v.w += bi;
+  }
+  if (relu) v = make_float4(pw_relu(v.x), pw_relu(v.y), pw_relu(v.z), pw_relu(v.w));
+  if (residual) {
+    float4 rv;
+    if (vec_io) rv = *reinterpret_cast<const float4 *>(residual + o);
+    else rv = make_float4(residual[o], residual[o + 1], residual[o + 2], residual[o + 3]);
+    if (res_is_mask) v = make_float4(pw_masked(v.x, rv.x), pw_masked(v.y, rv.y), pw_masked(v.z, rv.z), pw_masked(v.w, rv.w));
+    else v = make_float4(v.x + rv.x, v.y + rv.y, v.z + rv.z, v.w + rv.w);
+  }
+  if (relu_after) v = make_float4(pw_relu(v.x), pw_relu(v.y), pw_relu(v.z), pw_relu(v.w));
+  if (vec_io) {
+    *reinterpret_cast<float4 *>(y + o) = v;
+  } else {
+    y[o] = v.x;
+    y[o + 1] = v.y;
+    y[o + 2] = v.z;
+    y[o + 3] = v.w;
+  }
+}
+
 // ---------------------------------------------------------------- weight gradient
 // gw[co][ci] = sum_b sum_l g[b][co][l] x[b][ci][l]  (g = grad_out, optionally masked by ReLU'),
 // gb[co] = sum_b sum_l g[b][co][l].  M = cout, N = cin, K = the b * len positions: a huge reduction with a
@@ -680,26 +822,42 @@ extern "C" int mvp_pointwise_mfma(int b, int cin, int cout, int len, const float
                                group, y, 0, nullptr, stream);
 }
 
-extern "C" int mvp_pointwise_mfma_ex(int b, int cin, int cout, int len, const float *x, const float *xmask,
-                                     const float *w, int ldw, int w_kmajor, const float *bias, int bias_per_cloud,
-                                     const float *residual, int flags, int group, float *y, int m_split, float *y2,
-                                     void *stream) {
+// The argument checks of mvp_pointwise_mfma_ex (the split-K entry point shares them): an error code, or MVP_OK with
+// `empty` set where there is nothing to compute; ldw = 0 becomes the dense row length.
+static int pw_ex_check(int b, int cin, int cout, int len, const float *x, const float *xmask, const float *w, int &ldw,
+                       int w_kmajor, const float *bias, int bias_per_cloud, const float *residual, int flags, int group,
+                       const float *y, int m_split, const float *y2, bool &empty) {
+  empty = false;
   if (b < 0 || cin <= 0 || cout <= 0 || len < 0) return MVP_EBADSHAPE;
   if ((flags & ~(MVP_PW_RELU | MVP_PW_RELU_AFTER | MVP_PW_RES_IS_MASK | MVP_PW_X_RELU)) != 0) return MVP_EBADARG;
   if ((flags & MVP_PW_RES_IS_MASK) && !residual) return MVP_EBADARG;
   if ((flags & MVP_PW_X_RELU) && xmask) return MVP_EBADARG;
   if (m_split != 0 && (m_split < 0 || m_split >= cout || (m_split & 31) != 0 || !y2 || residual || group != 1)) return MVP_EBADARG;
   if (bias_per_cloud && !bias) return MVP_EBADARG;
-  const int bias_bs = bias_per_cloud ? cout : 0;
   if (group < 1 || group > 32 || (group & (group - 1)) != 0) return MVP_EBADSHAPE;
   if ((len & 3) != 0 || len % group != 0 || b > 65535) return MVP_EBADSHAPE;
-  if (b == 0 || len == 0) return MVP_OK;
+  if (b == 0 || len == 0) {
+    empty = true;
+    return MVP_OK;
+  }
   if (!x || !w || !y) return MVP_EBADARG;
   if ((reinterpret_cast<uintptr_t>(x) & 15) != 0 || (reinterpret_cast<uintptr_t>(xmask) & 15) != 0) return MVP_EBADARG;
   if (ldw == 0) ldw = w_kmajor ? cout : cin;                    // dense rows
   if (ldw < (w_kmajor ? cout : cin)) return MVP_EBADARG;
   if (w_kmajor && ((cout & 3) != 0 || (ldw & 3) != 0 || (reinterpret_cast<uintptr_t>(w) & 15) != 0)) return MVP_EBADARG;
   if (!w_kmajor && (ldw & 3) == 0 && (reinterpret_cast<uintptr_t>(w) & 15) != 0) return MVP_EBADARG;
+  return MVP_OK;
+}
+
+extern "C" int mvp_pointwise_mfma_ex(int b, int cin, int cout, int len, const float *x, const float *xmask,
+                                     const float *w, int ldw, int w_kmajor, const float *bias, int bias_per_cloud,
+                                     const float *residual, int flags, int group, float *y, int m_split, float *y2,
+                                     void *stream) {
+  bool empty;
+  const int rc = pw_ex_check(b, cin, cout, len, x, xmask, w, ldw, w_kmajor, bias, bias_per_cloud, residual, flags, group, y,
+                             m_split, y2, empty);
+  if (rc != MVP_OK || empty) return rc;
+  const int bias_bs = bias_per_cloud ? cout : 0;
   hipStream_t st = as_stream(stream);
   const bool big = cout > 64;
   const int bm = big ? 128 : 64;
@@ -726,6 +884,89 @@ extern "C" int mvp_pointwise_mfma_ex(int b, int cin, int cout, int len, const fl
 #undef MVP_MM
 #undef MVP_MM_
   return check_launch("mvp_pointwise_mfma");
+}
+
+// ---- split along K (ABI 20) ----
+static int splitk_tile_n(int len) { return len <= 64 ? 64 : 128; }
+
+// Suggested chunk of the reduction, 0 = do not split: a reduction longer than 512 whose output tiles (128 x 128, 64 rows
+// for cout <= 64, 64 columns for len <= 64) do not fill the chip's 512 workgroup slots is cut into as many chunks as fill
+// them, each at least 128 long, at most 16.
+extern "C" int mvp_pointwise_mfma_splitk_plan(int b, int cin, int cout, int len) {
+  if (b <= 0 || cin <= 512 || cout <= 0 || len <= 0 || (len & 3) != 0 || b > 65535) return 0;
+  const int bm = cout > 64 ? 128 : 64, bn = splitk_tile_n(len);
+  const long long tiles = (long long)((cout + bm - 1) / bm) * ((len + bn - 1) / bn) * b;
+  if (tiles >= 512) return 0;
+  long long splits = (512 + tiles - 1) / tiles;
+  if (splits > cin / 128) splits = cin / 128;
+  if (splits > 16) splits = 16;
+  if (splits < 2) return 0;
+  const int per = (int)((cin + splits - 1) / splits);
+  return (per + 15) / 16 * 16;
+}
+
+extern "C" long long mvp_pointwise_mfma_splitk_scratch_bytes(int b, int cin, int cout, int len, int k_chunk) {
+  if (b <= 0 || cin <= 0 || cout <= 0 || len <= 0 || (len & 3) != 0 || b > 65535) return 0;
+  if (k_chunk <= 0 || (k_chunk & 15) != 0) return 0;
+  const long long splits = ((long long)cin + k_chunk - 1) / k_chunk;
+  if (splits > 32) return 0;
+  return splits * b * cout * len * 4;
+}
+
+extern "C" int mvp_pointwise_mfma_splitk(int b, int cin, int cout, int len, const float *x, const float *xmask,
+                                         const float *w, int ldw, int w_kmajor, const float *bias, int bias_per_cloud,
+                                         const float *residual, int flags, float *y, int k_chunk, void *scratch,
+                                         long long scratch_bytes, void *stream) {
+  if (k_chunk <= 0 || (k_chunk & 15) != 0) return MVP_EBADARG;
+  if (cin <= 0 || k_chunk >= cin)                            // one split (or a bad shape, which the plain call refuses)
+    return mvp_pointwise_mfma_ex(b, cin, cout, len, x, xmask, w, ldw, w_kmajor, bias, bias_per_cloud, residual, flags, 1, y,
+                                 0, nullptr, stream);
+  const int splits = (int)(((long long)cin + k_chunk - 1) / k_chunk);
+  if (splits > 32) return MVP_EBADSHAPE;
+  bool empty;
+  const int rc = pw_ex_check(b, cin, cout, len, x, xmask, w, ldw, w_kmajor, bias, bias_per_cloud, residual, flags, 1, y, 0,
+                             nullptr, empty);
+  if (rc != MVP_OK || empty) return rc;
+  const long long need = mvp_pointwise_mfma_splitk_scratch_bytes(b, cin, cout, len, k_chunk);
+  if (need == 0) return MVP_EBADSHAPE;
+  if (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15) != 0 || scratch_bytes < need) return MVP_EBADARG;
+  hipStream_t st = as_stream(stream);
+  const bool big = cout > 64, narrow = splitk_tile_n(len) == 64;
+  const int bm = big ? 128 : 64, bn = narrow ? 64 : 128;
+  const long long total = (long long)((cout + bm - 1) / bm) * ((len + bn - 1) / bn) * splits * b;
+  const long long nwg = (total + 7) / 8 * 8;
+  const long long quads = (long long)b * cout * len / 4, nred = (quads + 255) / 256;
+  if (nwg > 2147483647LL || nred > 2147483647LL) return MVP_EBADSHAPE;
+  const int a_vec = w_kmajor ? 1 : ((ldw & 3) == 0);            // 16-byte loads along k need aligned rows
+  float *partial = static_cast<float *>(scratch);
+#define MVP_SK_(TM, TN, MODE, MK, XR)                                                                                      \
+  hipLaunchKernelGGL((pointwise_mfma_splitk_kernel<TM, TN, 16, MODE, MK, XR>), dim3((unsigned)nwg), dim3(kMmThreads), 0, st, \
+                     cout, len, cin, b, k_chunk, splits, w, ldw, a_vec, x, xmask, partial)
+#define MVP_SK(TM, TN, MODE)                                             \
+  do {                                                                   \
+    if (xmask) MVP_SK_(TM, TN, MODE, true, false);                       \
+    else if (flags & MVP_PW_X_RELU) MVP_SK_(TM, TN, MODE, false, true);  \
+    else MVP_SK_(TM, TN, MODE, false, false);                            \
+  } while (0)
+#define MVP_SK_TILE(TM, TN)            \
+  do {                                 \
+    if (w_kmajor) MVP_SK(TM, TN, kXC); \
+    else MVP_SK(TM, TN, kKC);          \
+  } while (0)
+  if (big) {
+    if (narrow) MVP_SK_TILE(2, 1);
+    else MVP_SK_TILE(2, 2);
+  } else {
+    if (narrow) MVP_SK_TILE(1, 1);
+    else MVP_SK_TILE(1, 2);
+  }
+#undef MVP_SK_TILE
+#undef MVP_SK
+#undef MVP_SK_
+  const int vec_io = ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(residual)) & 15) == 0;
+  hipLaunchKernelGGL(pointwise_splitk_reduce_kernel, dim3((unsigned)nred), dim3(256), 0, st, quads, cout, len, splits, partial,
+                     bias, bias_per_cloud ? cout : 0, residual, flags, vec_io, y);
+  return check_launch("mvp_pointwise_mfma_splitk");
 }
 
 // (W x + bias).max over the positions of every cloud, fused: val (b, cout), idx (b, cout) = the first position that

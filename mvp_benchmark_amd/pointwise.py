@@ -18,10 +18,12 @@ and the weight dense and 16-byte aligned; "fits" = _gemm_fits.
     forward            mfma      mfma and fits(cout x cin) and (cout >= 32 or cin <=                     mvp_pointwise_mfma_ex
                                  MFMA_SKINNY_FWD_MAX_CIN); under `function` also MFMA_TRAIN or small,
                                  on the contiguous copies; under `none` only from dense tensors
+                       splitk    MFMA_SPLIT_K: as `mfma`, but fits fails and _split_k gives a chunk      mvp_pointwise_mfma_splitk
                        library   otherwise                                                               _library_conv
   data gradient        small     small                                                                   mvp_pointwise_dgrad
     (_plan_conv_       mfma      MFMA_DGRAD, mfma but for x's layout, cin % 4 == 0, fits(cin x cout)     mvp_pointwise_mfma_ex (W^T)
-     backward)         gemm      otherwise                                                               torch.matmul
+     backward)         splitk    MFMA_SPLIT_K: as `mfma`, but fits fails and _split_k gives a chunk      mvp_pointwise_mfma_splitk (W^T)
+                       gemm      otherwise                                                               torch.matmul
   weight gradient      mfma      mfma, not small, cin >= MFMA_WGRAD_MIN_CIN, B * L >=                    mvp_pointwise_wgrad_mfma_ex
                                  MFMA_WGRAD_MIN_POSITIONS, the kernel's scratch query > 0
                        small     small, x 16-byte aligned (the kernel refuses a view at an odd offset)   mvp_pointwise_wgrad
@@ -30,7 +32,9 @@ and the weight dense and 16-byte aligned; "fits" = _gemm_fits.
     premask                      ReLU and a wanted gradient whose route is not mfma (those mask on load) aten.threshold_backward
   pointwise_conv_fused fused     dense, mfma, fits forward, (x needs a gradient: cin % 4 == 0 and fits   one GEMM
     (_plan_fused)                the data gradient), the weight-gradient conditions (also for
-                                 inference), float32 residual / cloud_bias, not relu with a residual
+                                 inference), float32 residual / cloud_bias, not relu with a residual;
+                                 with MFMA_SPLIT_K "fits" also where _split_k gives a chunk (that GEMM
+                                 then runs on mvp_pointwise_mfma_splitk)
                        composed  otherwise                                                               pointwise_conv + elementwise
   pointwise_conv_dual  stacked   cout1 % 32 == 0, both layers `fused`, the stacked forward `mfma`        one GEMM, two outputs
     (_plan_dual)       separate  otherwise                                                               two pointwise_conv
@@ -48,7 +52,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.autograd import Function
 
-from ._lib import call, pointwise_max_backward_scratch_bytes, pointwise_wgrad_mfma_scratch_bytes, pointwise_wgrad_scratch_bytes
+from ._lib import (call, pointwise_max_backward_scratch_bytes, pointwise_mfma_splitk_plan, pointwise_mfma_splitk_scratch_bytes,
+                   pointwise_wgrad_mfma_scratch_bytes, pointwise_wgrad_scratch_bytes)
 
 # The route selectors stay module globals under these names (not completion/op_config.py): bench.py, the tools and
 # several tests assign them, and the planners read them at call time.
@@ -82,6 +87,11 @@ MFMA_WGRAD_MIN_POSITIONS = 16384   # B * L below this: too few slabs of position
 # rounds 8-12; VRCNet 18.39 -> 18.45.  Not faster, so the default stays MIOpen for the forward and the weight gradient of
 # those layers; True = no MIOpen call at all in the training path.
 LIBRARY_IS_GEMM = False
+# The GEMMs _gemm_fits refuses (a reduction > 512 with too few output tiles: ECG's bottleneck layers and their data gradients)
+# on mvp_pointwise_mfma_splitk -- partial tiles per chunk of the reduction, then a fixed-order sum with the epilogue -- instead
+# of the library.  Off: whether it pays is decided from profiles/pointwise_splitk.txt and profiles/pointwise_splitk_ecg_ab.txt
+# (tools/bench_splitk.py, tools/ab_flag.py); with it off every planner returns what it returned before the route existed.
+MFMA_SPLIT_K = False
 
 _WGRAD_SCRATCH = {}   # (device, stream) -> one growing workspace for the partial tiles (no allocator churn)
 
@@ -140,6 +150,15 @@ def _gemm_fits(batch, m, k, length):
     return -(-m // bm) * -(-length // 128) * batch >= 512
 
 
+def _split_k(batch, m, k, length):
+    """The chunk of the reduction for mvp_pointwise_mfma_splitk where the per-cloud GEMM (m x k) (k x length) is one
+    _gemm_fits refuses and the library's plan splits it; 0 = not split (always, with MFMA_SPLIT_K off).  Pure; the planners
+    and the Functions both ask here, so a plan and its call cannot disagree."""
+    if not MFMA_SPLIT_K or _gemm_fits(batch, m, k, length):
+        return 0
+    return pointwise_mfma_splitk_plan(batch, k, m, length)
+
+
 def _ours(d):
     return d.cuda and d.f32 and d.dim in (3, 4) and d.L > 0 and d.L % 4 == 0 and d.B <= 65535
 
@@ -161,6 +180,16 @@ def _mfma_fwd(d):
     return _mfma(d) and _gemm_fits(d.B, d.cout, d.cin, d.L) and (d.cout >= 32 or d.cin <= MFMA_SKINNY_FWD_MAX_CIN)
 
 
+def _fwd_route(d):
+    """Forward route of a layer whose tensors the kernels take: `mfma`, `splitk` (everything of _mfma_fwd holds but
+    _gemm_fits, and _split_k gives a chunk) or `library`."""
+    if _mfma_fwd(d):
+        return "mfma"
+    if _mfma(d) and (d.cout >= 32 or d.cin <= MFMA_SKINNY_FWD_MAX_CIN) and _split_k(d.B, d.cout, d.cin, d.L) > 0:
+        return "splitk"
+    return "library"
+
+
 ConvPlan = namedtuple("ConvPlan", "via fwd layer")     # layer: what _PointwiseConv saves for its backward plan
 BackwardPlan = namedtuple("BackwardPlan", "dgrad wgrad premask wgrad_bytes")
 MaxPlan = namedtuple("MaxPlan", "via fwd layer")
@@ -168,29 +197,30 @@ MaxPlan = namedtuple("MaxPlan", "via fwd layer")
 
 def _plan_conv(d, wants_grad):
     """pointwise_conv: via `function` (_PointwiseConv), `autograd` (the library's convolution, differentiated by PyTorch) or
-    `none` (no gradient wanted); forward `mfma` or `library`."""
+    `none` (no gradient wanted); forward `mfma`, `splitk` or `library`."""
     routed = d.cuda and d.f32 and d.x_dense and d.w_dense and d.nonempty and (_mfma(d) or _small(d))
     if wants_grad and ((routed and (MFMA_TRAIN or _small(d))) or (not routed and USE_MFMA and d.cuda and d.f32 and d.nonempty)):
         # (not routed: shapes no kernel of ours covers -- positions not a multiple of 4, strided tensors: the library's forward,
         # but STILL _PointwiseConv's backward: its data gradient is a batched GEMM, never MIOpen's implicit-GEMM backward-data
         # kernel, which reads out of bounds on such shapes)
         d = _densified(d)
-        return ConvPlan("function", "mfma" if (MFMA_TRAIN or _small(d)) and _mfma_fwd(d) else "library", d)
+        return ConvPlan("function", _fwd_route(d) if MFMA_TRAIN or _small(d) else "library", d)
     if wants_grad or not USE_MFMA:
         return ConvPlan("autograd", "library", d)
-    return ConvPlan("none", "mfma" if routed and _mfma_fwd(d) else "library", d)
+    return ConvPlan("none", _fwd_route(d) if routed else "library", d)
 
 
 def _plan_conv_backward(d, relu, has_bias, need_x, need_w, need_b):
-    """_PointwiseConv.backward from the Layer saved at forward time: data gradient `small` / `mfma` / `gemm`, weight (+ bias)
+    """_PointwiseConv.backward from the Layer saved at forward time: data gradient `small` / `mfma` / `splitk` / `gemm`, weight (+ bias)
     gradient `mfma` / `small` / `gemm` / `miopen` (None: not needed), whether grad_out is masked by ReLU' up front for the
     routes that do not mask on load, and the MFMA weight gradient's scratch size (queried once, here)."""
     dgrad = wgrad = None
     nbytes = 0
     if need_x:
         # <= 64 x 64 channels: mvp_pointwise_dgrad (11-26 us, at or below the MFMA kernel)
-        dgrad = "small" if _small(d) else \
-            "mfma" if MFMA_DGRAD and _mfma(d, x_too=False) and d.cin % 4 == 0 and _gemm_fits(d.B, d.cin, d.cout, d.L) else "gemm"
+        kernel = MFMA_DGRAD and _mfma(d, x_too=False) and d.cin % 4 == 0
+        dgrad = "small" if _small(d) else "mfma" if kernel and _gemm_fits(d.B, d.cin, d.cout, d.L) else \
+            "splitk" if kernel and _split_k(d.B, d.cin, d.cout, d.L) > 0 else "gemm"
     if need_w or need_b:
         if d.cin >= MFMA_WGRAD_MIN_CIN and _mfma(d) and not _small(d) and d.B * d.L >= MFMA_WGRAD_MIN_POSITIONS:
             nbytes = pointwise_wgrad_mfma_scratch_bytes(d.B, d.cin, d.cout, d.L, has_bias)
@@ -200,14 +230,17 @@ def _plan_conv_backward(d, relu, has_bias, need_x, need_w, need_b):
     return BackwardPlan(dgrad, wgrad, premask, nbytes)
 
 
-def _plan_fused(d, need_x, relu=False, residual=False, float32_operands=True):
+def _plan_fused(d, need_x, relu=False, residual=False, float32_operands=True, split_k=True):
     """pointwise_conv_fused: `fused` -- all three passes of the layer on the MFMA kernels (the fused prologues / epilogues live
     there only), one GEMM -- or `composed`.  relu with a residual is composed: the fused backward masks by the final output,
-    which is not the inner ReLU's mask there."""
+    which is not the inner ReLU's mask there.  A GEMM _gemm_fits refuses also counts where _split_k gives it a chunk
+    (split_k=False: not for this caller -- the stacked form has no split kernel)."""
     # (the skinny-forward rule of _mfma_fwd is not applied: 544 -> 16 at 384 points costs 0.031 ms here against the
     # library's 0.024, the passes over the 53 MB input that the fused prologue saves cost 0.06)
-    ok = _mfma(d) and not (relu and residual) and float32_operands and _gemm_fits(d.B, d.cout, d.cin, d.L) \
-        and (not need_x or (d.cin % 4 == 0 and _gemm_fits(d.B, d.cin, d.cout, d.L))) \
+    def fits(m, k):
+        return _gemm_fits(d.B, m, k, d.L) or (split_k and _split_k(d.B, m, k, d.L) > 0)
+    ok = _mfma(d) and not (relu and residual) and float32_operands and fits(d.cout, d.cin) \
+        and (not need_x or (d.cin % 4 == 0 and fits(d.cin, d.cout))) \
         and d.B * d.L >= MFMA_WGRAD_MIN_POSITIONS and pointwise_wgrad_mfma_scratch_bytes(d.B, d.cin, d.cout, d.L, True) > 0
     return "fused" if ok else "composed"
 
@@ -219,7 +252,7 @@ def _fused_routes(x, weight, need_x):
 
 def _plan_dual(d1, d2, need_x):
     """pointwise_conv_dual: `stacked` (one GEMM over both weights, two outputs) or `separate`."""
-    ok = d1.cout % 32 == 0 and _plan_fused(d1, need_x) == "fused" and _plan_fused(d2, need_x) == "fused" \
+    ok = d1.cout % 32 == 0 and _plan_fused(d1, need_x, split_k=False) == "fused" and _plan_fused(d2, need_x, split_k=False) == "fused" \
         and _mfma_fwd(d1._replace(cout=d1.cout + d2.cout))
     return "stacked" if ok else "separate"
 
@@ -265,7 +298,7 @@ def _one_bias(bias, cloud_bias):
 
 
 def mfma_linear(x, w2d, bias=None, relu=False, residual=None, group=1, w_kmajor=False, xmask=None, x_relu=False,
-                relu_after=False, res_is_mask=False, bias_per_cloud=False, m_split=0):
+                relu_after=False, res_is_mask=False, bias_per_cloud=False, m_split=0, k_chunk=0):
     """y = epilogue(W x) for x (B, Cin, ...) contiguous float32 CUDA, W = w2d (Cout, Cin) -- or its
     transpose (Cin, Cout) with w_kmajor; with xmask, x counts as 0 where xmask <= 0 (aten.threshold_backward's select:
     x passes where xmask is NaN, an Inf of x is dropped, not multiplied); with x_relu, x counts as relu(x) (a NaN stays
@@ -273,7 +306,11 @@ def mfma_linear(x, w2d, bias=None, relu=False, residual=None, group=1, w_kmajor=
     max over groups of `group` consecutive positions of the flattened trailing dimensions, + residual (or, with
     res_is_mask, zero where residual <= 0 and unchanged elsewhere, also where residual is NaN), ReLU again with
     relu_after.  Every ReLU keeps a NaN like torch.relu, the group maximum is NaN if a member is (torch.max).
-    m_split > 0: two outputs, the rows below m_split and the others -> (y, y2).  No autograd."""
+    m_split > 0: two outputs, the rows below m_split and the others -> (y, y2).
+    k_chunk > 0 (a multiple of 16; group == 1, no m_split): mvp_pointwise_mfma_splitk -- the reduction in chunks of k_chunk
+    over separate workgroups, summed in ascending order before the epilogue.  No autograd."""
+    if k_chunk and (group != 1 or m_split):
+        raise ValueError("k_chunk: the split-K kernel has neither the group maximum nor two outputs")
     B = x.size(0)
     cin = x.size(1)
     cout = w2d.size(1) if w_kmajor else w2d.size(0)
@@ -289,6 +326,15 @@ def mfma_linear(x, w2d, bias=None, relu=False, residual=None, group=1, w_kmajor=
     w2d, ldw = (w2d, 0) if w_kmajor else _rows_of_4(w2d, cin)
     flags = (PW_RELU if relu else 0) | (PW_RELU_AFTER if relu_after else 0) | (PW_RES_IS_MASK if res_is_mask else 0) \
         | (PW_X_RELU if x_relu else 0)
+    if k_chunk:
+        scratch, nbytes = None, 0
+        if k_chunk < cin:          # (one chunk is the plain kernel: no scratch)
+            nbytes = pointwise_mfma_splitk_scratch_bytes(B, cin, cout, length, k_chunk)
+            # stream-ordered reuse: the reduce kernel has read it before the next call on this stream writes
+            scratch = _wgrad_scratch(x.device, nbytes) if nbytes else None
+        call("mvp_pointwise_mfma_splitk", x.device, B, cin, cout, length, x, xmask, w2d, ldw, int(w_kmajor), bias,
+             int(bias_per_cloud), residual, flags, y, int(k_chunk), scratch, nbytes)
+        return y
     call("mvp_pointwise_mfma_ex", x.device, B, cin, cout, length, x, xmask, w2d, ldw, int(w_kmajor), bias, int(bias_per_cloud),
          residual, flags, int(group), y, int(m_split), y2)
     return (y, y2) if m_split else y
@@ -330,8 +376,9 @@ class _PointwiseConv(Function):
         ctx.has_bias = bias is not None
         ctx.relu = relu
         x, weight = x.contiguous(), weight.contiguous()     # (a permuted view: the kernels of the backward pass take dense tensors)
-        if plan.fwd == "mfma":
-            y = mfma_linear(x, weight.view(d.cout, d.cin), bias, relu=relu)
+        if plan.fwd in ("mfma", "splitk"):
+            y = mfma_linear(x, weight.view(d.cout, d.cin), bias, relu=relu,
+                            k_chunk=_split_k(d.B, d.cout, d.cin, d.L) if plan.fwd == "splitk" else 0)
         else:
             y = _library_conv(x, weight, bias, d)
             if relu:
@@ -353,8 +400,9 @@ class _PointwiseConv(Function):
         mask = y if ctx.relu else None
         gy_masked = torch.ops.aten.threshold_backward(gy, y, 0) if plan.premask else gy
         gx = gw = gb = None
-        if plan.dgrad == "mfma":
-            gx = mfma_linear(gy, weight.view(d.cout, d.cin), w_kmajor=True, xmask=mask)       # W^T (gy . relu')
+        if plan.dgrad in ("mfma", "splitk"):
+            gx = mfma_linear(gy, weight.view(d.cout, d.cin), w_kmajor=True, xmask=mask,       # W^T (gy . relu')
+                             k_chunk=_split_k(d.B, d.cin, d.cout, d.L) if plan.dgrad == "splitk" else 0)
         elif plan.dgrad == "small":
             # few channels: W^T gy in one pass over gy (mvp_pointwise_dgrad) -- not the library's implicit-GEMM
             # kernel, one variant of which reads out of bounds on these shapes (csrc/pointwise.hip)
@@ -397,8 +445,9 @@ def pointwise_conv(x, weight, bias=None, relu=False):
     plan = _plan_conv(d, _wants_grad(weight, x, bias))
     if plan.via == "function":
         return _PointwiseConv.apply(x, weight, bias, relu, plan)
-    if plan.fwd == "mfma":                 # inference
-        return mfma_linear(x, weight.view(d.cout, d.cin), bias, relu=relu)
+    if plan.fwd in ("mfma", "splitk"):     # inference
+        return mfma_linear(x, weight.view(d.cout, d.cin), bias, relu=relu,
+                           k_chunk=_split_k(d.B, d.cout, d.cin, d.L) if plan.fwd == "splitk" else 0)
     if plan.via == "autograd":
         y = (F.conv1d if d.dim == 3 else F.conv2d)(x, weight, bias)
     else:
@@ -439,7 +488,8 @@ class _PointwiseConvFused(Function):
         gx = gw = gb = gcb = None
         if need_x:
             gx = mfma_linear(gy, weight.view(cout, cin), w_kmajor=True, xmask=mask,
-                             residual=x if ctx.relu_in else None, res_is_mask=ctx.relu_in)
+                             residual=x if ctx.relu_in else None, res_is_mask=ctx.relu_in,
+                             k_chunk=_split_k(x.size(0), cin, cout, x[0, 0].numel()))     # (0 where the GEMM fits: _plan_fused)
         if need_w or need_b:
             gw, gb = mfma_wgrad(x, gy, cout, cin, ctx.has_bias, gymask=mask, x_relu=ctx.relu_in)
             gw = gw.view_as(weight)
@@ -452,7 +502,8 @@ class _PointwiseConvFused(Function):
 def _fused_forward(x, weight, bias, cloud_bias, residual, relu_in, relu, relu_after):
     cout, cin = weight.shape[:2]
     return mfma_linear(x, weight.view(cout, cin), _one_bias(bias, cloud_bias), relu=relu, residual=residual, x_relu=relu_in,
-                       relu_after=relu_after, bias_per_cloud=cloud_bias is not None)
+                       relu_after=relu_after, bias_per_cloud=cloud_bias is not None,
+                       k_chunk=_split_k(x.size(0), cout, cin, x[0, 0].numel()))           # (0 where the GEMM fits: _plan_fused)
 
 
 def pointwise_conv_fused(x, weight, bias=None, relu_in=False, relu=False, residual=None, relu_after=False, cloud_bias=None):
