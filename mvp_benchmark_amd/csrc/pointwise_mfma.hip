@@ -13,7 +13,8 @@
 // epilogue fused (+ bias, ReLU, + residual, max over groups of consecutive columns)
 // and ReLU' applied to the incoming gradient on load in both backward passes.
 //
-// One compute core, three passes.  An operand tile is staged through LDS in one of
+// One compute core, three passes: the pipelined K loop of the forward / data-gradient kernel, of its split-K form and of the
+// weight-gradient kernel is one text, pointwise_k_loop.inc.  An operand tile is staged through LDS in one of
 // two images, chosen by how the operand lies in memory, so that every global read
 // and every LDS write is a 16-byte access whatever the pass:
 //   * "x-contiguous" ([k][x] in memory: the activations X / gY per cloud, and the
@@ -209,6 +210,16 @@ __device__ __forceinline__ void pw_mma(f32x16 (&acc)[TM][TN], const float (&a)[T
       for (int n = 0; n < TN; ++n) acc[i][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][j], b[n][j], acc[i][n], 0, 0, 0);
 }
 
+// sum += the N floats at row (an LDS image, 16-byte aligned), four at a time
+template <int N>
+__device__ __forceinline__ void pw_add_row(float &sum, const float *row) {
+#pragma unroll
+  for (int k = 0; k < N; k += 4) {
+    const float4 q = *reinterpret_cast<const float4 *>(row + k);
+    sum += (q.x + q.y) + (q.z + q.w);
+  }
+}
+
 // keys (see pointwise_mfma_kernel, ROWMAX) -> val[i] = the row's maximum, idx[i] = the first position that attains it
 __global__ void pointwise_rowmax_unpack_kernel(long long total, const unsigned long long *__restrict__ keys,
                                                float *__restrict__ val, int *__restrict__ idx) {
@@ -227,7 +238,23 @@ __device__ __forceinline__ long long pw_work_item(long long total) {
   return (long long)(blockIdx.x & 7) * per + (blockIdx.x >> 3);
 }
 
+// C/D layout of the 32 x 32 matrix instruction: register r of a lane holds column lane & 31 (lrow) and row
+// (r & 3) + 8 (r >> 2) + 4 (lane >> 5) of its block.  pw_acc_row: that row counted from `base`, the block's first row (0 and
+// lk = 0: its distance from the lane's first row); pw_tile_col: the column of block j of wave column wn (tn blocks wide) in
+// the tile that starts at n0.  (The sums keep this order: another association moves instructions.)
+__device__ __forceinline__ constexpr int pw_acc_row(int base, int r, int lk) { return base + (r & 3) + 8 * (r >> 2) + 4 * lk; }
+__device__ __forceinline__ constexpr int pw_tile_col(int n0, int wn, int tn, int j, int lrow) {
+  return n0 + wn * 32 * tn + j * 32 + lrow;
+}
+
 // ------------------------------------------------------------------- forward / data gradient
+// The K loop (pointwise_k_loop.inc) of this kernel and of its split-K form below: the slabs of the K-range [ks, ke), the
+// weight tile is A, the cloud's activation tile (with its mask, or as relu(x)) is B; the range is never empty (K > 0).
+#define PW_K_SETUP const int s_begin = 0, s_end = (ke - ks + BK - 1) / BK;
+#define PW_K_FETCH(s)                                                                                      \
+  pw_fetch<BM, BK, AMODE, false>(ra, ram, a, nullptr, lda, m0, M, ks + (s) * BK, ke, a_vec != 0, t);       \
+  pw_fetch<BN, BK, kXC, MASKED>(rb, rbm, xb, mb, N, n0, N, ks + (s) * BK, ke, true, t)
+#define PW_K_SLAB_DONE(buf)
 // Per cloud  Y (M x N) = A (M x K) X (K x N): A = the weight, (M, K) row-major [AMODE kKC: forward] or (K, M)
 // row-major [kXC: the data gradient multiplies by W^T]; X, xmask (K x N), Y per cloud.
 // ROWMAX (round 5): the epilogue keeps only the maximum of every output row over ALL positions of its cloud, and where it
@@ -270,59 +297,25 @@ __global__ __launch_bounds__(kMmThreads) __attribute__((amdgpu_waves_per_eu(TM =
 
   if (t < BM) sbias[t] = (bias && m0 + t < M) ? bias[(size_t)cloud * bias_bs + m0 + t] : 0.f;   // bias_bs = M: a bias per cloud
 
-  f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  constexpr int ks = 0;                                    // the whole reduction
+  const int ke = K;
+  constexpr int BMODE = kXC;
+  constexpr bool AMASK = false, BMASK = MASKED, BRELU = XRELU, EARLY = false, MAY_BE_EMPTY = false;
+#include "pointwise_k_loop.inc"
 
-  PwRegs<IA::vecs> ra;
-  PwRegs<IB::vecs> rb;
-  PwRegs<1> rnone;
-  PwRegs<MASKED ? IB::vecs : 1> rbm;
-  const int nk = (K + BK - 1) / BK;
-  pw_fetch<BM, BK, AMODE, false>(ra, rnone, a, nullptr, lda, m0, M, 0, K, a_vec != 0, t);
-  pw_fetch<BN, BK, kXC, MASKED>(rb, rbm, xb, mb, N, n0, N, 0, K, true, t);
-  pw_stash<BM, BK, AMODE, false>(As[0], ra, rnone, t);
-  pw_stash<BN, BK, kXC, MASKED, XRELU>(Bs[0], rb, rbm, t);
-  __syncthreads();
-  for (int s = 0; s < nk; ++s) {
-    const int buf = s & 1;
-    if (s + 1 < nk) {                                   // in flight while this slab computes
-      pw_fetch<BM, BK, AMODE, false>(ra, rnone, a, nullptr, lda, m0, M, (s + 1) * BK, K, a_vec != 0, t);
-      pw_fetch<BN, BK, kXC, MASKED>(rb, rbm, xb, mb, N, n0, N, (s + 1) * BK, K, true, t);
-    }
-#pragma unroll
-    for (int kg = 0; kg < BK / 8; ++kg) {
-      float av[TM][4], bv[TN][4];
-      pw_frag<TM, BM, BK, AMODE>(av, As[buf], wm * 32 * TM, kg, lrow, lk);
-      pw_frag<TN, BN, BK, kXC>(bv, Bs[buf], wn * 32 * TN, kg, lrow, lk);
-      pw_mma<TM, TN>(acc, av, bv);
-      if (kg == kPwStashAt(BK / 8, false) && s + 1 < nk) {
-        // the next slab goes into the other buffer (nobody reads it in this step) while the matrix
-        // core works through the instructions issued so far: the stores' latency is covered
-        pw_stash<BM, BK, AMODE, false>(As[buf ^ 1], ra, rnone, t);
-        pw_stash<BN, BK, kXC, MASKED, XRELU>(Bs[buf ^ 1], rb, rbm, t);
-      }
-    }
-    if (s + 1 < nk) __syncthreads();
-  }
-
-  // ---- epilogue.  C/D layout of 32x32: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+  // ---- epilogue (the accumulators' rows and columns: pw_acc_row, pw_tile_col)
   if constexpr (ROWMAX) {
     unsigned long long *keys = reinterpret_cast<unsigned long long *>(y) + (size_t)cloud * M;
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int lr = wm * 32 * TM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+        const int lr = pw_acc_row(wm * 32 * TM + i * 32, r, lk);
         const float bi = sbias[lr];
         unsigned hi = 0u, lo = 0u;            // this lane's best of its TN columns: value bits (0: none), ~column
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-          const int col = n0 + wn * 32 * TN + j * 32 + lrow;
+          const int col = pw_tile_col(n0, wn, TN, j, lrow);
           float v = acc[i][j][r] + bi;
           if (relu) v = pw_relu(v);
           // order-preserving key, > 0; -0 counts as +0 (the first position of a tie wins, as torch.max reports) and a NaN
@@ -352,16 +345,16 @@ __global__ __launch_bounds__(kMmThreads) __attribute__((amdgpu_waves_per_eu(TM =
     for (int i = 0; i < TM; ++i) {
       float bv[16];                                      // the rows' biases first: independent LDS reads, one wait
 #pragma unroll
-      for (int r = 0; r < 16; ++r) bv[r] = sbias[wm * 32 * TM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk];
+      for (int r = 0; r < 16; ++r) bv[r] = sbias[pw_acc_row(wm * 32 * TM + i * 32, r, lk)];
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
-        const int col = n0 + wn * 32 * TN + j * 32 + lrow;
+        const int col = pw_tile_col(n0, wn, TN, j, lrow);
         float *yc = yb + (size_t)(m0 + wm * 32 * TM + i * 32 + 4 * lk) * N + col;
         const int rows_left = M - (m0 + wm * 32 * TM + i * 32 + 4 * lk);   // rows of this lane that exist
         if (col < N) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int dr = (r & 3) + 8 * (r >> 2);
+            const int dr = pw_acc_row(0, r, 0);
             float v = acc[i][j][r] + bv[r];
             v = relu_any ? pw_relu(v) : v;
             if (dr < rows_left) yc[(size_t)dr * N] = v;
@@ -384,26 +377,26 @@ __global__ __launch_bounds__(kMmThreads) __attribute__((amdgpu_waves_per_eu(TM =
     for (int i = 0; i < TM; ++i) {
       float bv[16];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) bv[r] = sbias[wm * 32 * TM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk];
+      for (int r = 0; r < 16; ++r) bv[r] = sbias[pw_acc_row(wm * 32 * TM + i * 32, r, lk)];
       const int blk = m0 + wm * 32 * TM + i * 32;        // first row of this 32-row block
       float *yb = blk < ms ? y1b : y2b;
       const int rows_left = (blk < ms ? ms : M) - (blk + 4 * lk);
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
-        const int col = n0 + wn * 32 * TN + j * 32 + lrow;
+        const int col = pw_tile_col(n0, wn, TN, j, lrow);
         const size_t o0 = (size_t)(blk + 4 * lk) * N + col;
         if (col < N) {
           float rv[16];
           if (rbse) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-              const int dr = (r & 3) + 8 * (r >> 2);
+              const int dr = pw_acc_row(0, r, 0);
               rv[r] = dr < rows_left ? rbse[o0 + (size_t)dr * N] : 0.f;
             }
           }
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int dr = (r & 3) + 8 * (r >> 2);
+            const int dr = pw_acc_row(0, r, 0);
             float v = acc[i][j][r] + bv[r];
             v = relu ? pw_relu(v) : v;
             if (rbse) v = res_is_mask ? pw_masked(v, rv[r]) : v + rv[r];
@@ -420,10 +413,12 @@ __global__ __launch_bounds__(kMmThreads) __attribute__((amdgpu_waves_per_eu(TM =
   for (int i = 0; i < TM; ++i)
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
+      // pw_tile_col, spelled out: through the call, this epilogue alone compiles to other instructions (16 fewer per row
+      // block in the 12 instances that have it; not measured, so not taken here)
       const int col = n0 + wn * 32 * TN + j * 32 + lrow;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int lr = wm * 32 * TM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+        const int lr = pw_acc_row(wm * 32 * TM + i * 32, r, lk);
         const int row = m0 + lr;
         float v = acc[i][j][r] + sbias[lr];
         if (relu) v = pw_relu(v);
@@ -454,8 +449,9 @@ __global__ __launch_bounds__(kMmThreads) __attribute__((amdgpu_waves_per_eu(TM =
 // multiple of BK, so a chunk's slabs -- and with them the order of every matrix instruction -- are those of the kernel
 // above run on that K-slice alone), a workgroup takes one (tile, chunk) and writes its raw accumulators to
 // partial[split][cloud][M][N]; pointwise_splitk_reduce_kernel adds the chunks in ascending order and applies the epilogue.
-// No atomics: the result is a fixed expression.  The prologues (xmask, ReLU of x) stay on load.  A kernel of its own, so
-// that the instances above compile to what they were.  TN = 1 (a 64-column tile) serves len <= 64.
+// No atomics: the result is a fixed expression.  The prologues (xmask, ReLU of x) stay on load.  A kernel of its own (the
+// K loop is the one above, on [ks, ke)), so that the instances above compile to what they were.  TN = 1 (a 64-column tile)
+// serves len <= 64.
 template <int TM, int TN, int BK, int AMODE, bool MASKED, bool XRELU>
 __global__ __launch_bounds__(kMmThreads) __attribute__((amdgpu_waves_per_eu(TM == 2 ? 3 : 5))) void pointwise_mfma_splitk_kernel(
     int M, int N, int K, int nb, int k_chunk, int splits, const float *__restrict__ a, int a_ld, int a_vec,
@@ -483,57 +479,26 @@ __global__ __launch_bounds__(kMmThreads) __attribute__((amdgpu_waves_per_eu(TM =
   const float *mb = xmask ? xmask + (size_t)cloud * K * N : nullptr;
   const size_t lda = a_ld;
 
-  f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  constexpr int BMODE = kXC;
+  constexpr bool AMASK = false, BMASK = MASKED, BRELU = XRELU, EARLY = false, MAY_BE_EMPTY = false;
+#include "pointwise_k_loop.inc"
+#undef PW_K_SETUP
+#undef PW_K_FETCH
+#undef PW_K_SLAB_DONE
 
-  PwRegs<IA::vecs> ra;
-  PwRegs<IB::vecs> rb;
-  PwRegs<1> rnone;
-  PwRegs<MASKED ? IB::vecs : 1> rbm;
-  const int nk = (ke - ks + BK - 1) / BK;
-  pw_fetch<BM, BK, AMODE, false>(ra, rnone, a, nullptr, lda, m0, M, ks, ke, a_vec != 0, t);
-  pw_fetch<BN, BK, kXC, MASKED>(rb, rbm, xb, mb, N, n0, N, ks, ke, true, t);
-  pw_stash<BM, BK, AMODE, false>(As[0], ra, rnone, t);
-  pw_stash<BN, BK, kXC, MASKED, XRELU>(Bs[0], rb, rbm, t);
-  __syncthreads();
-  for (int s = 0; s < nk; ++s) {
-    const int buf = s & 1;
-    if (s + 1 < nk) {                                   // in flight while this slab computes
-      pw_fetch<BM, BK, AMODE, false>(ra, rnone, a, nullptr, lda, m0, M, ks + (s + 1) * BK, ke, a_vec != 0, t);
-      pw_fetch<BN, BK, kXC, MASKED>(rb, rbm, xb, mb, N, n0, N, ks + (s + 1) * BK, ke, true, t);
-    }
-#pragma unroll
-    for (int kg = 0; kg < BK / 8; ++kg) {
-      float av[TM][4], bv[TN][4];
-      pw_frag<TM, BM, BK, AMODE>(av, As[buf], wm * 32 * TM, kg, lrow, lk);
-      pw_frag<TN, BN, BK, kXC>(bv, Bs[buf], wn * 32 * TN, kg, lrow, lk);
-      pw_mma<TM, TN>(acc, av, bv);
-      if (kg == kPwStashAt(BK / 8, false) && s + 1 < nk) {
-        pw_stash<BM, BK, AMODE, false>(As[buf ^ 1], ra, rnone, t);
-        pw_stash<BN, BK, kXC, MASKED, XRELU>(Bs[buf ^ 1], rb, rbm, t);
-      }
-    }
-    if (s + 1 < nk) __syncthreads();
-  }
-
-  // partial[split][cloud][row][col]; C/D layout of 32x32: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+  // partial[split][cloud][row][col]
   float *pp = partial + ((size_t)split * nb + cloud) * M * N;
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
-      const int col = n0 + wn * 32 * TN + j * 32 + lrow;
+      const int col = pw_tile_col(n0, wn, TN, j, lrow);
       const int row0 = m0 + wm * 32 * TM + i * 32 + 4 * lk;
       float *pc = pp + (size_t)row0 * N + col;
       if (col < N) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int dr = (r & 3) + 8 * (r >> 2);
+          const int dr = pw_acc_row(0, r, 0);
           if (dr < M - row0) pc[(size_t)dr * N] = acc[i][j][r];
         }
       }
@@ -621,67 +586,38 @@ __global__ __launch_bounds__(kMmThreads) void pointwise_wgrad_mfma_kernel(
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int wm = wave >> 1, wn = wave & 1, lrow = lane & 31, lk = lane >> 5;
 
-  f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  const bool do_bias = with_bias && n0 == 0;
-  constexpr int kParts = kMmThreads / BM;                   // threads per row of the g tile
-  float bsum = 0.f;
-
-  PwRegs<IA::vecs> ra;
-  PwRegs<IB::vecs> rb;
-  PwRegs<1> rnone;
-  PwRegs<MASKED ? IA::vecs : 1> ram;
-  auto fetch = [&](int gs) {
-    const int cloud = gs / slabs_per_cloud, l0 = (gs - cloud * slabs_per_cloud) * BK;
-    const size_t og = (size_t)cloud * cout * len, ox = (size_t)cloud * cin * len;
-    pw_fetch<BM, BK, kKC, MASKED>(ra, ram, g + og, MASKED ? gmask + og : nullptr, len, m0, cout, l0, len, true, t);
-    pw_fetch<BN, BK, kKC, false>(rb, rnone, x + ox, nullptr, len, n0, cin, l0, len, true, t);
+  // The K loop: slabs of positions, the g tile (with its mask) is A, the x tile (or relu(x)) is B.  (fetch is a lambda, as it
+  // has been: spelled out at its two places like the forward kernels' step, the 16 instances compile to 40-220 fewer
+  // instructions in the same registers -- a change of its own, to be measured before it is taken.)
+  constexpr int AMODE = kKC, BMODE = kKC;
+  constexpr bool AMASK = MASKED, BMASK = false, BRELU = XRELU, EARLY = true, MAY_BE_EMPTY = true;
+#define PW_K_SETUP                                                                                                     \
+  const bool do_bias = with_bias && n0 == 0;                                                                           \
+  constexpr int kParts = kMmThreads / BM; /* threads per row of the g tile */                                          \
+  float bsum = 0.f;                                                                                                    \
+  auto fetch = [&](int gs) {                                                                                           \
+    const int cloud = gs / slabs_per_cloud, l0 = (gs - cloud * slabs_per_cloud) * BK;                                  \
+    const size_t og = (size_t)cloud * cout * len, ox = (size_t)cloud * cin * len;                                      \
+    pw_fetch<BM, BK, kKC, MASKED>(ra, ram, g + og, MASKED ? gmask + og : nullptr, len, m0, cout, l0, len, true, t);    \
+    pw_fetch<BN, BK, kKC, false>(rb, rbm, x + ox, nullptr, len, n0, cin, l0, len, true, t);                            \
   };
-  if (s_begin < s_end) {
-    fetch(s_begin);
-    pw_stash<BM, BK, kKC, MASKED>(As[0], ra, ram, t);
-    pw_stash<BN, BK, kKC, false, XRELU>(Bs[0], rb, rnone, t);
-  }
-  __syncthreads();
-  for (int s = s_begin; s < s_end; ++s) {
-    const int buf = (s - s_begin) & 1;
-    if (s + 1 < s_end) fetch(s + 1);
-#pragma unroll
-    for (int kg = 0; kg < BK / 8; ++kg) {
-      float av[TM][4], bv[TN][4];
-      pw_frag<TM, BM, BK, kKC>(av, As[buf], wm * 32 * TM, kg, lrow, lk);
-      pw_frag<TN, BN, BK, kKC>(bv, Bs[buf], wn * 32 * TN, kg, lrow, lk);
-      pw_mma<TM, TN>(acc, av, bv);
-      if (kg == kPwStashAt(BK / 8, true) && s + 1 < s_end) {
-        pw_stash<BM, BK, kKC, MASKED>(As[buf ^ 1], ra, ram, t);
-        pw_stash<BN, BK, kKC, false, XRELU>(Bs[buf ^ 1], rb, rnone, t);
-      }
-    }
-    if (do_bias) {
-      const float *row = As[buf] + (t / kParts) * IA::ld + (t % kParts) * (BK / kParts);
-#pragma unroll
-      for (int k = 0; k < BK / kParts; k += 4) {
-        const float4 q = *reinterpret_cast<const float4 *>(row + k);
-        bsum += (q.x + q.y) + (q.z + q.w);
-      }
-    }
-    if (s + 1 < s_end) __syncthreads();
-  }
+#define PW_K_FETCH(s) fetch(s)
+#define PW_K_SLAB_DONE(buf) \
+  if (do_bias) pw_add_row<BK / kParts>(bsum, As[buf] + (t / kParts) * IA::ld + (t % kParts) * (BK / kParts))
+#include "pointwise_k_loop.inc"
+#undef PW_K_SETUP
+#undef PW_K_FETCH
+#undef PW_K_SLAB_DONE
   // partial[split][co][ci]
   float *pp = partial + (size_t)split * cout * cin;
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
-      const int col = n0 + wn * 32 * TN + j * 32 + lrow;
+      const int col = pw_tile_col(n0, wn, TN, j, lrow);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = m0 + wm * 32 * TM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+        const int row = pw_acc_row(m0 + wm * 32 * TM + i * 32, r, lk);
         if (row < cout && col < cin) pp[(size_t)row * cin + col] = acc[i][j][r];
       }
     }
@@ -735,16 +671,35 @@ __global__ __launch_bounds__(256) void pointwise_wgrad_reduce_kernel(int cin, in
 #define MVP_WG_BK 32
 #endif
 constexpr int kWgBK = MVP_WG_BK;
-// workgroups of the weight-gradient kernel resident at once: BK 32 -> 74 KB of LDS, 240 VGPRs: 2 per CU; BK 16: 3 per CU
+// workgroups of the weight-gradient kernel resident at once.  BK 32, 128 x 128 tiles: 72 KB of LDS (73728 bytes) and 164-184
+// VGPRs, so the LDS allows 2 per CU (160 KB) and the registers 2 waves per SIMD = 2 workgroups; BK 16: 3 per CU
 constexpr int kWgSlots = kWgBK == 32 ? 512 : 768;
+
+// ---- host side: shapes, tiles, grids
+// What every GEMM entry point here takes: positive sizes, rows of x that are whole 16-byte groups, at most max_b clouds.
+static bool pw_shape_ok(int b, int cin, int cout, int len, int max_b = 2147483647) {
+  return b > 0 && b <= max_b && cin > 0 && cout > 0 && len > 0 && (len & 3) == 0;
+}
+static int pw_tile(int n) { return n > 64 ? 128 : 64; }      // rows (columns) of the tile for n output rows (columns)
+static long long pw_tiles(int rows, int bm, int cols, int bn) {
+  return (long long)((rows + bm - 1) / bm) * ((cols + bn - 1) / bn);
+}
+// The grid for bm x bn tiles over rows x cols with per_tile work items each, rounded up to the 8 XCDs (pw_work_item); 0
+// where it does not fit a grid dimension.
+static long long pw_grid(int rows, int bm, int cols, int bn, long long per_tile) {
+  const long long nwg = (pw_tiles(rows, bm, cols, bn) * per_tile + 7) / 8 * 8;
+  return nwg > 2147483647LL ? 0 : nwg;
+}
+// 16-byte loads of the weight along k need aligned rows (a k-major weight is read along its rows: checked by the caller)
+static int pw_a_vec(int w_kmajor, int ldw) { return w_kmajor ? 1 : ((ldw & 3) == 0); }
 
 // runs of position slabs: splits x tiles ~ one wave of workgroups
 static void wgrad_plan(int b, int cin, int cout, int len, int &slabs_per_cloud, int &slabs_per_split, int &splits) {
-  const int bm = cout > 64 ? 128 : 64, bn = cin > 64 ? 128 : 64;
-  const long long tiles = (long long)((cout + bm - 1) / bm) * ((cin + bn - 1) / bn);
+  const int bm = pw_tile(cout), bn = pw_tile(cin);
+  const long long tiles = pw_tiles(cout, bm, cin, bn);
   slabs_per_cloud = (len + kWgBK - 1) / kWgBK;
   const long long slabs = (long long)b * slabs_per_cloud;
-  // (64 x 64 tiles: 37 KB of LDS, 100 VGPRs -- four workgroups per CU)
+  // (64 x 64 tiles: 36 KB of LDS, 72-84 VGPRs -- four workgroups per CU)
   long long want = (bm == 64 && bn == 64 ? 2 * kWgSlots : kWgSlots) / tiles;
   if (want < 1) want = 1;
   if (want > slabs) want = slabs;
@@ -758,7 +713,7 @@ static void wgrad_plan(int b, int cin, int cout, int len, int &slabs_per_cloud, 
 using namespace mvp;
 
 extern "C" long long mvp_pointwise_wgrad_mfma_scratch_bytes(int b, int cin, int cout, int len, int with_bias) {
-  if (b <= 0 || cin <= 0 || cout <= 0 || len <= 0 || (len & 3) != 0) return 0;
+  if (!pw_shape_ok(b, cin, cout, len)) return 0;
   if ((long long)b * ((len + kWgBK - 1) / kWgBK) > 2147483647LL) return 0;
   int spc, sps, splits;
   wgrad_plan(b, cin, cout, len, spc, sps, splits);
@@ -785,10 +740,9 @@ extern "C" int mvp_pointwise_wgrad_mfma_ex(int b, int cin, int cout, int len, co
   hipStream_t st = as_stream(stream);
   float *partial = static_cast<float *>(scratch);
   float *pbias = partial + (size_t)splits * cout * cin;
-  const int bm = cout > 64 ? 128 : 64, bn = cin > 64 ? 128 : 64;
-  const long long total = (long long)((cout + bm - 1) / bm) * ((cin + bn - 1) / bn) * splits;
-  const long long nwg = (total + 7) / 8 * 8;
-  if (nwg > 2147483647LL) return MVP_EBADSHAPE;
+  const int bm = pw_tile(cout), bn = pw_tile(cin);
+  const long long nwg = pw_grid(cout, bm, cin, bn, splits);
+  if (nwg == 0) return MVP_EBADSHAPE;
 #define MVP_WG_(TM, TN, MK, XR)                                                                                             \
   hipLaunchKernelGGL((pointwise_wgrad_mfma_kernel<TM, TN, kWgBK, MK, XR>), dim3((unsigned)nwg), dim3(kMmThreads), 0, st, b, \
                      cin, cout, len, spc, sps, splits, x, gy, gymask, with_bias, partial, pbias)
@@ -860,11 +814,9 @@ extern "C" int mvp_pointwise_mfma_ex(int b, int cin, int cout, int len, const fl
   const int bias_bs = bias_per_cloud ? cout : 0;
   hipStream_t st = as_stream(stream);
   const bool big = cout > 64;
-  const int bm = big ? 128 : 64;
-  const long long total = (long long)((cout + bm - 1) / bm) * ((len + 127) / 128) * b;
-  const long long nwg = (total + 7) / 8 * 8;
-  if (nwg > 2147483647LL) return MVP_EBADSHAPE;
-  const int a_vec = w_kmajor ? 1 : ((ldw & 3) == 0);            // 16-byte loads along k need aligned rows
+  const long long nwg = pw_grid(cout, pw_tile(cout), len, 128, b);
+  if (nwg == 0) return MVP_EBADSHAPE;
+  const int a_vec = pw_a_vec(w_kmajor, ldw);
 #define MVP_MM_(TM, MODE, MK, XR)                                                                                       \
   hipLaunchKernelGGL((pointwise_mfma_kernel<TM, 2, 16, MODE, MK, false, XR>), dim3((unsigned)nwg), dim3(kMmThreads), 0, st, cout, \
                      len, cin, b, w, ldw, a_vec, x, xmask, bias, residual, flags, group, y, bias_bs, m_split, y2)
@@ -893,9 +845,8 @@ static int splitk_tile_n(int len) { return len <= 64 ? 64 : 128; }
 // for cout <= 64, 64 columns for len <= 64) do not fill the chip's 512 workgroup slots is cut into as many chunks as fill
 // them, each at least 128 long, at most 16.
 extern "C" int mvp_pointwise_mfma_splitk_plan(int b, int cin, int cout, int len) {
-  if (b <= 0 || cin <= 512 || cout <= 0 || len <= 0 || (len & 3) != 0 || b > 65535) return 0;
-  const int bm = cout > 64 ? 128 : 64, bn = splitk_tile_n(len);
-  const long long tiles = (long long)((cout + bm - 1) / bm) * ((len + bn - 1) / bn) * b;
+  if (!pw_shape_ok(b, cin, cout, len, 65535) || cin <= 512) return 0;
+  const long long tiles = pw_tiles(cout, pw_tile(cout), len, splitk_tile_n(len)) * b;
   if (tiles >= 512) return 0;
   long long splits = (512 + tiles - 1) / tiles;
   if (splits > cin / 128) splits = cin / 128;
@@ -906,7 +857,7 @@ extern "C" int mvp_pointwise_mfma_splitk_plan(int b, int cin, int cout, int len)
 }
 
 extern "C" long long mvp_pointwise_mfma_splitk_scratch_bytes(int b, int cin, int cout, int len, int k_chunk) {
-  if (b <= 0 || cin <= 0 || cout <= 0 || len <= 0 || (len & 3) != 0 || b > 65535) return 0;
+  if (!pw_shape_ok(b, cin, cout, len, 65535)) return 0;
   if (k_chunk <= 0 || (k_chunk & 15) != 0) return 0;
   const long long splits = ((long long)cin + k_chunk - 1) / k_chunk;
   if (splits > 32) return 0;
@@ -932,12 +883,10 @@ extern "C" int mvp_pointwise_mfma_splitk(int b, int cin, int cout, int len, cons
   if (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15) != 0 || scratch_bytes < need) return MVP_EBADARG;
   hipStream_t st = as_stream(stream);
   const bool big = cout > 64, narrow = splitk_tile_n(len) == 64;
-  const int bm = big ? 128 : 64, bn = narrow ? 64 : 128;
-  const long long total = (long long)((cout + bm - 1) / bm) * ((len + bn - 1) / bn) * splits * b;
-  const long long nwg = (total + 7) / 8 * 8;
+  const long long nwg = pw_grid(cout, pw_tile(cout), len, splitk_tile_n(len), (long long)splits * b);
   const long long quads = (long long)b * cout * len / 4, nred = (quads + 255) / 256;
-  if (nwg > 2147483647LL || nred > 2147483647LL) return MVP_EBADSHAPE;
-  const int a_vec = w_kmajor ? 1 : ((ldw & 3) == 0);            // 16-byte loads along k need aligned rows
+  if (nwg == 0 || nred > 2147483647LL) return MVP_EBADSHAPE;
+  const int a_vec = pw_a_vec(w_kmajor, ldw);
   float *partial = static_cast<float *>(scratch);
 #define MVP_SK_(TM, TN, MODE, MK, XR)                                                                                      \
   hipLaunchKernelGGL((pointwise_mfma_splitk_kernel<TM, TN, 16, MODE, MK, XR>), dim3((unsigned)nwg), dim3(kMmThreads), 0, st, \
@@ -987,11 +936,9 @@ extern "C" int mvp_pointwise_mfma_max(int b, int cin, int cout, int len, const f
   hipStream_t st = as_stream(stream);
   if (hipMemsetAsync(keys, 0, (size_t)b * cout * 8, st) != hipSuccess) return MVP_ELAUNCH;
   const bool big = cout > 64;
-  const int bm = big ? 128 : 64;
-  const long long total = (long long)((cout + bm - 1) / bm) * ((len + 127) / 128) * b;
-  const long long nwg = (total + 7) / 8 * 8;
-  if (nwg > 2147483647LL) return MVP_EBADSHAPE;
-  const int a_vec = (ldw & 3) == 0;
+  const long long nwg = pw_grid(cout, pw_tile(cout), len, 128, b);
+  if (nwg == 0) return MVP_EBADSHAPE;
+  const int a_vec = pw_a_vec(0, ldw);
   const float *none = nullptr;
   float *y = reinterpret_cast<float *>(keys);
   const int group = 1;
