@@ -1000,6 +1000,7 @@ __global__ __launch_bounds__(256) void emd_grad_kernel(
 //   MVP_EMD_CLUSTER / MVP_EMD_SAME_XCD / MVP_EMD_SPLIT / MVP_EMD_RESIDENT_CAP   the same four knobs
 //   MVP_EMD_PLAN_ROUND / MVP_EMD_PLAN_EVERY / MVP_EMD_PLAN_WIDTHS               the tiered launch's plan (emd_lean.hip)
 //   MVP_EMD_TIERS_FAIL                                                          "the tiered kernel does not fit this device"
+//   MVP_EMD_POLL_DISTRUST                                                       gathered-bid rounds of odd count re-read their bid records (emd_lean_round_gathered.inc)
 // split: 0 one kernel runs every round; 1: the rounds after the last four-bidders-per-wave round run in the lean kernel
 // (emd_lean.hip); 2: + cluster widths dealt out by load at round 300 (33..64 clouds of >= 4096 points); 3: + clouds of
 // <= 4096 points finish LDS-resident on one workgroup, in a launch of their own (emd_resident.hip); 4: ... inside the lean
@@ -1010,10 +1011,11 @@ struct EmdKnobs {
   int plan_round, plan_every;     // split == 2: round of the first plan; rounds per planned launch
   unsigned long long plan_widths; // widths of an XCD's 8 cloud slots, heaviest first, 4 bits each
   int res_cap;                    // split == 3: unassigned persons at which a cloud of <= 4096 points moves into LDS (emd_resident.hip)
+  int poll_distrust;              // MVP_TEST_HOOKS only: bit 2 of the lean launch's fast_ok
 };
 // The compiled-in defaults: of the process-wide knobs and of every mvp_emd_forward_plan call.
 static EmdKnobs emd_default_knobs() {
-  return EmdKnobs{kMaxCluster, 1, 5, 300, 4096, 0ull, 16};   // plan_widths 0: from the loads (MVP_EMD_PLAN_WIDTHS=8,5,4,4,3,3,3,2 fixes them)
+  return EmdKnobs{kMaxCluster, 1, 5, 300, 4096, 0ull, 16, 0};   // plan_widths 0: from the loads (MVP_EMD_PLAN_WIDTHS=8,5,4,4,3,3,3,2 fixes them)
 }
 // The four public fields (mvp_emd_configure's arguments, MvpEmdPlan's members) into `k`: negative = keep.  All four are
 // checked before anything is written, so a rejected call changes nothing.
@@ -1035,6 +1037,7 @@ static EmdKnobs &emd_knobs_locked() {   // (callers hold g_knob_mutex)
     if (const char *e = getenv("MVP_EMD_SAME_XCD")) v.same_xcd = atoi(e) != 0;
     if (const char *e = getenv("MVP_EMD_SPLIT")) v.split = atoi(e) < 0 ? 0 : atoi(e) > 5 ? 5 : atoi(e);
     if (const char *e = getenv("MVP_EMD_RESIDENT_CAP")) v.res_cap = atoi(e) < 1 ? 1 : atoi(e) > kResList ? kResList : atoi(e);
+    if (const char *e = getenv("MVP_EMD_POLL_DISTRUST")) v.poll_distrust = atoi(e) != 0;
     if (const char *e = getenv("MVP_EMD_PLAN_ROUND")) v.plan_round = atoi(e) < 1 ? 1 : atoi(e);
     if (const char *e = getenv("MVP_EMD_PLAN_EVERY")) v.plan_every = atoi(e) < 64 ? 64 : atoi(e);
     if (const char *e = getenv("MVP_EMD_PLAN_WIDTHS")) {   // e.g. 8,6,4,4,3,3,2,2
@@ -1135,7 +1138,7 @@ static int emd_forward_with(const EmdKnobs &knobs, int b, int n, const float *xy
     w = 1;
     (void)emd_launch<1>(b, n, xyz1, xyz2, dist, assignment, eps, iters, sbase, lean, 0, st);
   }
-  if (lean && emd_lean_launch(b, n, w, xyz1, dist, assignment, eps, iters, sbase, knobs.same_xcd | (knobs.split >= 5 ? 2 : 0),
+  if (lean && emd_lean_launch(b, n, w, xyz1, dist, assignment, eps, iters, sbase, knobs.same_xcd | (knobs.split >= 5 ? 2 : 0) | (knobs.poll_distrust ? 4 : 0),
                               knobs.plan_round, knobs.split >= 2 ? knobs.plan_every : 0, knobs.plan_widths,
                               knobs.split >= 4 ? knobs.res_cap : knobs.split == 3 ? -knobs.res_cap : 0, st) != hipSuccess)
     return check_launch("mvp_emd_forward");

@@ -220,7 +220,7 @@ __device__ __forceinline__ int emd_lean_body(LeanShared &sh, const int cloud, co
   // Gathered-bid rounds (entered below once at most kGCap persons are unassigned; their number never grows): `eg`
   // counts them (tags of the bid granules), `goff` = this member's first position in the cloud-wide order of bids.
   bool gm_now = false;
-  const bool gm_ok = WB != 1 && n <= kGMaxN && (fast_ok & 2) != 0;   // (fast_ok: bit 0 = same-XCD stores, bit 1 = gathered-bid rounds)
+  const bool gm_ok = WB != 1 && n <= kGMaxN && (fast_ok & 2) != 0;   // (fast_ok: bit 0 = same-XCD stores, bit 1 = gathered-bid rounds, bit 2 = the MVP_TEST_HOOKS build's MVP_EMD_POLL_DISTRUST)
   unsigned eg = (unsigned)resume->epoch_g;
   int goff = 0, gi = 0;
   int gU = 0;   // this member's bidders of the coming gathered-bid round (with goff: derived where the lists are counted)
