@@ -15,12 +15,16 @@ by tests/test_model_golden.py); the defaults are the measured-faster ones (DESIG
   fps_beside_losses    VRCNet training: the decoder's FPS on a side lane while the main stream computes the losses of the two
                        outputs that already exist
   singleton_sk         SK_SA_module with ONE kernel (the shipped cfg): attention == 1 exactly, the fusion passes not issued
+  dense_edge_conv      ECG's Dense_conv: gather, ReLU, stack layers and the max over k in one kernel each way
+                       (mvp_dense_edge_conv).  OFF by default: not bit-identical to the composed route (another summation
+                       order); measured ECG step 17.57 -> 15.88 ms (profiles/dense_edge_conv.txt), the default is a later change
 """
 
 
 class OpLayerConfig:
     __slots__ = ("gather_sum", "gather_max", "side_lanes", "stacked_projections", "skip_full_fps_of_gt",
-                 "conv_before_interp", "folded_conv", "singleton_sk", "fused_activations", "fps_beside_losses")
+                 "conv_before_interp", "folded_conv", "singleton_sk", "fused_activations", "fps_beside_losses",
+                 "dense_edge_conv")
 
     def __init__(self):
         self.reset()
@@ -36,6 +40,7 @@ class OpLayerConfig:
         self.singleton_sk = True
         self.fused_activations = True
         self.fps_beside_losses = True
+        self.dense_edge_conv = False
 
     def as_dict(self):
         return {k: getattr(self, k) for k in self.__slots__}

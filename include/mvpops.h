@@ -43,7 +43,7 @@ extern "C" {
 #define MVP_ELAUNCH (-3)
 
 /* ABI version of this header; bumped on any signature change. */
-#define MVP_ABI_VERSION 20
+#define MVP_ABI_VERSION 21
 int mvp_abi_version(void);
 
 /* hipGetErrorString of the last launch failure seen on the calling thread
@@ -460,6 +460,33 @@ int mvp_share_gather_sum(int b, int share, int cw, int k, int n_src, int n, cons
 int mvp_share_gather_sum_grad(int b, int share, int cw, int k, int n_src, int n, const float *w,
                               const float *v, const int *idx, const float *grad_out,
                               float *grad_w, float *grad_vals, void *stream);
+
+/* Dense edge convolution of ECG (completion/models/ecg.py:36-65, Dense_conv: conv / ReLU / cat / max over the k
+ * neighbours, op by op on (B, ., N, k) tensors; no native counterpart in the reference) with the per-edge values kept
+ * in registers.  layers = dense_n - 1 stack layers (0..2), g in {8,16,24,32}, 1 <= k <= 64, n <= 65536; anything else
+ * is MVP_EBADSHAPE.  Per cloud, point p, neighbour slot j:
+ *   edge[:, j] = relu(a[:, p] + nb[idx[j, p], :])
+ *   y_i[:, j]  = act_i(W_i [edge; y_1; ..; y_{i-1}][:, j] + ctr_i[:, p])   act_i = ReLU for i < layers, none for the last
+ *   out[:, p]  = [max_j edge, max_j y_1, .., max_j y_layers],  arg = the FIRST maximal j per channel (mvp_gather_max's rule)
+ * a (b,g,n), ctr (b,layers*g,n), idx (b,k,n) int32 k-major (clamped into [0,n)), out and arg (b,(layers+1)*g,n) are
+ * channel-major.  nb (b,n,g) is POINT-major and 16-byte aligned: a neighbour's g values are one contiguous read.
+ * w: layer i (1-based) is (g, i*g) row-major over [edge, y_1 .. y_{i-1}], layers back to back, g*g*layers*(layers+1)/2
+ * floats.  Every y is an fma chain over ascending input channels started from the centre term.  With layers == 0,
+ * ctr, w, grad_ctr, grad_w and scratch may be NULL.  Non-finite inputs: unspecified.
+ * _grad recomputes the per-edge values from the inputs and arg and writes (never accumulates into) grad_a (b,g,n),
+ * grad_ctr (b,layers*g,n), grad_w and -- unless grad_edge is NULL -- grad_edge (b,g,k,n), the gradient at the pre-ReLU
+ * edge sum, to be scattered into grad_nb (b,g,n) by mvp_group_points_grad(_ws); grad_a is its sum over k.  grad_w: one
+ * partial sum per workgroup of 64 points in `scratch` (mvp_dense_edge_conv_scratch_bytes: 4 * b * ceil(n/64) * the
+ * floats of w bytes, at least 4; 0 = shape not covered), added up in a fixed order by a second launch: no float
+ * atomics, the same bits on every run. */
+long long mvp_dense_edge_conv_scratch_bytes(int b, int g, int layers, int k, int n);
+int mvp_dense_edge_conv(int b, int g, int layers, int k, int n, const float *a, const float *nb,
+                        const int *idx, const float *ctr, const float *w, float *out, int *arg,
+                        void *stream);
+int mvp_dense_edge_conv_grad(int b, int g, int layers, int k, int n, const float *a, const float *nb,
+                             const int *idx, const float *ctr, const float *w, const int *arg,
+                             const float *grad_out, float *grad_a, float *grad_edge, float *grad_ctr,
+                             float *grad_w, void *scratch, long long scratch_bytes, void *stream);
 
 /* ------------------------------------------- grouped-feature MLP on MFMA */
 

@@ -49,6 +49,8 @@ SIGNATURES = {
     "mvp_share_weighted_sum_grad": "iiiiippppp",
     "mvp_share_gather_sum": "iiiiiipppp",
     "mvp_share_gather_sum_grad": "iiiiiipppppp",
+    "mvp_dense_edge_conv": "iiiiippppppp",
+    "mvp_dense_edge_conv_grad": "iiiiippppppppppppq",
     "mvp_pointwise_wgrad": "iiiipppppq",
     "mvp_pointwise_dgrad": "iiiippp",
     "mvp_kabsch_svd3": "ipppppp",
@@ -66,7 +68,7 @@ SIGNATURES = {
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "f": ctypes.c_float,
        "q": ctypes.c_longlong}
 
-ABI_VERSION = 20  # MVP_ABI_VERSION of include/mvpops.h this binding was written against
+ABI_VERSION = 21  # MVP_ABI_VERSION of include/mvpops.h this binding was written against
 
 # default of mvp_emd_configure's `split` knob (csrc/emd.hip: emd_knobs)
 EMD_DEFAULT_SPLIT = 5
@@ -118,6 +120,8 @@ def load():
     lib.mvp_pointwise_max_backward_scratch_bytes.argtypes = [ctypes.c_int] * 4
     lib.mvp_share_gather_sum_lds_bytes.restype = ctypes.c_longlong
     lib.mvp_share_gather_sum_lds_bytes.argtypes = [ctypes.c_int] * 2
+    lib.mvp_dense_edge_conv_scratch_bytes.restype = ctypes.c_longlong
+    lib.mvp_dense_edge_conv_scratch_bytes.argtypes = [ctypes.c_int] * 5
     for name, sig in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype = ctypes.c_int
@@ -273,10 +277,16 @@ def pointwise_max_backward_scratch_bytes(b, cin, cout, length):
     return int(load().mvp_pointwise_max_backward_scratch_bytes(int(b), int(cin), int(cout), int(length)))
 
 
+def dense_edge_conv_scratch_bytes(b, g, layers, k, n):
+    """Scratch of mvp_dense_edge_conv_grad's weight gradient (0: shape not covered)."""
+    return int(load().mvp_dense_edge_conv_scratch_bytes(int(b), int(g), int(layers), int(k), int(n)))
+
+
 def exported_symbols():
     """All entry points include/mvpops.h declares."""
     return ["mvp_abi_version", "mvp_last_hip_error", "mvp_emd_scratch_bytes", "mvp_emd_configure", "mvp_chamfer_scratch_bytes", "mvp_knn_scratch_bytes", "mvp_fps_scratch_bytes", "mvp_fps_cluster_scratch_bytes",
             "mvp_scatter_scratch_bytes", "mvp_pointwise_wgrad_scratch_bytes", "mvp_pointwise_wgrad_mfma_scratch_bytes",
             "mvp_pointwise_mfma_splitk_plan", "mvp_pointwise_mfma_splitk_scratch_bytes",
-            "mvp_pointwise_max_backward_scratch_bytes", "mvp_share_gather_sum_lds_bytes"] \
+            "mvp_pointwise_max_backward_scratch_bytes", "mvp_share_gather_sum_lds_bytes",
+            "mvp_dense_edge_conv_scratch_bytes"] \
         + list(SIGNATURES)

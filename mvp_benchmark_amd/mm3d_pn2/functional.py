@@ -18,7 +18,7 @@ import threading
 import torch
 from torch.autograd import Function
 
-from .._lib import call, fps_scratch_bytes, knn_scratch_bytes, scatter_scratch_bytes
+from .._lib import call, dense_edge_conv_scratch_bytes, fps_scratch_bytes, knn_scratch_bytes, scatter_scratch_bytes
 
 
 def _need_contiguous(*tensors):
@@ -446,9 +446,72 @@ class ShareGatherSum(Function):
         return grad_w, grad_v, None
 
 
+class DenseEdgeConv(Function):
+    """ECG's dense edge convolution (completion/models/edge_unet.py: Dense_conv) with every per-edge tensor kept in
+    registers (csrc/dense_edge_conv.hip).  L stack layers, growth rate g, per cloud, point n and neighbour slot j:
+        edge[:, j] = relu(a[:, n] + nb[:, idx[j, n]])
+        y_i[:, j]  = act_i(W_i [edge; y_1; ..; y_{i-1}][:, j] + ctr_i[:, n])      (ReLU for i < L, none for i = L)
+        out[:, n]  = [max_j edge, max_j y_1, .., max_j y_L]                        (first maximal j takes the gradient)
+    (a (B,g,N), nb (B,g,N), idx (B,k,N) int32 k-major, ctr (B,L*g,N), w (g*g*L*(L+1)/2,): layer i is (g, i*g)
+    row-major, layers back to back) -> (B,(L+1)*g,N); differentiable in a, nb, ctr and w.  The forward transposes nb once
+    (a neighbour's g values become one contiguous read) and saves the inputs and the arg-max slots; the BACKWARD
+    recomputes the per-edge values, emits grad_a, grad_ctr, grad_w (per-workgroup partial sums added in a fixed order:
+    deterministic) and -- when nb needs a gradient -- ONE (B,g,k,N) temporary, the gradient at the pre-ReLU edge sum,
+    which the grouping operator's scatter (inverted index, no atomics) sums into grad_nb.  Not part of the reference's
+    operator set."""
+
+    GROWTH = (8, 16, 24, 32)
+    MAX_LAYERS = 2
+    MAX_K = 64
+    MAX_N = 65536
+
+    @staticmethod
+    def covers(g, layers, k, n=1):
+        return g in DenseEdgeConv.GROWTH and 0 <= layers <= DenseEdgeConv.MAX_LAYERS and 1 <= k <= DenseEdgeConv.MAX_K \
+            and 0 <= n <= DenseEdgeConv.MAX_N
+
+    @staticmethod
+    def forward(ctx, a, nb, idx, ctr, w):
+        _need_contiguous(a, nb, idx, ctr, w)
+        B, g, N = a.shape
+        k = idx.shape[1]
+        layers = ctr.shape[1] // g
+        assert nb.shape == (B, g, N) and idx.shape == (B, k, N) and ctr.shape == (B, layers * g, N)
+        assert w.numel() == g * g * layers * (layers + 1) // 2 and DenseEdgeConv.covers(g, layers, k, N)
+        nb_rows = nb.detach().transpose(1, 2).contiguous()              # (B, N, g): point-major
+        out = _new(a, B, (layers + 1) * g, N)
+        arg = _new(a, B, (layers + 1) * g, N, dtype=torch.int32)
+        call("mvp_dense_edge_conv", a.device, B, g, layers, k, N, a, nb_rows, idx, ctr, w, out, arg)
+        ctx.save_for_backward(a, nb_rows, idx, ctr, w, arg)
+        ctx.mark_non_differentiable(idx)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        a, nb_rows, idx, ctr, w, arg = ctx.saved_tensors
+        B, g, N = a.shape
+        k = idx.shape[1]
+        layers = ctr.shape[1] // g
+        need_a, need_nb, _, need_ctr, need_w = ctx.needs_input_grad
+        grad_a, grad_ctr, grad_w = torch.empty_like(a), torch.empty_like(ctr), torch.empty_like(w)
+        grad_edge = _new(a, B, g, k, N) if need_nb else None           # (frozen nb: no temporary, no scatter pass)
+        nbytes = dense_edge_conv_scratch_bytes(B, g, layers, k, N)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
+        call("mvp_dense_edge_conv_grad", a.device, B, g, layers, k, N, a, nb_rows, idx, ctr, w, arg,
+             grad_out.data.contiguous(), grad_a, grad_edge, grad_ctr, grad_w, scratch, nbytes)
+        grad_nb = None
+        if need_nb:
+            grad_nb = _new(a, B, g, N)
+            scatter, sbytes, mode, key = _scatter_scratch(idx, None, B, N, k * N, 1)
+            call("mvp_group_points_grad_ws", a.device, B, g, N, k, N, grad_edge, idx, grad_nb, scatter, sbytes, mode)
+            _scatter_commit(key, idx, None, scatter)
+        return (grad_a if need_a else None, grad_nb, None, grad_ctr if need_ctr else None, grad_w if need_w else None)
+
+
 furthest_point_sample = FurthestPointSampling.apply
 share_weighted_sum = ShareWeightedSum.apply
 share_gather_sum = ShareGatherSum.apply
+dense_edge_conv = DenseEdgeConv.apply
 furthest_point_sample_with_dist = FurthestPointSamplingWithDist.apply
 ball_query = BallQuery.apply
 knn = KNN.apply
