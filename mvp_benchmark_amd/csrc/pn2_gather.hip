@@ -18,97 +18,111 @@
 // coalesced rows.  grouping_operation is the same kernel with the
 // (npoint, nsample) index array flattened.
 #include "common.h"
+#include "wave.h"
 
 namespace mvp {
 
 constexpr int kGThreads = 256;
 constexpr int kChan = 8;  // channels per workgroup strip
 
-__global__ __launch_bounds__(kGThreads) void gather_kernel(
-    int c, int n, int m, const float *__restrict__ points,
-    const int *__restrict__ idx, float *__restrict__ out) {
+// The taps of one output element: 1 source row (gather_points, grouping_operation) or 3 with their weights
+// (WEIGHTED: three_interpolate), read ONCE into registers from entry `e` of the index / weight arrays and used for
+// every channel of a strip.  `row` is one channel's row, in global memory or in LDS.
+template <bool WEIGHTED>
+struct Taps {
+  static constexpr int R = WEIGHTED ? 3 : 1;
+  int i[R];
+  float w[R];
+  template <typename E>
+  __device__ __forceinline__ Taps(const int *__restrict__ idx, const float *__restrict__ weight, E e) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) i[r] = idx[e * R + r];
+#pragma unroll
+    for (int r = 0; r < R; ++r) w[r] = WEIGHTED ? weight[e * R + r] : 1.f;
+  }
+  __device__ __forceinline__ float read(const float *row) const {
+    if constexpr (WEIGHTED) {
+      // w0*p0 + w1*p1 + w2*p2 == fma(w2,p2, fma(w1,p1, w0*p0)) (oracle chain)
+      return __builtin_fmaf(w[2], row[i[2]], __builtin_fmaf(w[1], row[i[1]], w[0] * row[i[0]]));
+    } else {
+      return row[i[0]];  // a copy, not a product with 1
+    }
+  }
+  __device__ __forceinline__ void add(float *row, float g) const {
+#pragma unroll
+    for (int r = 0; r < R; ++r) atomicAdd(row + i[r], WEIGHTED ? g * w[r] : g);
+  }
+};
+
+// grid (blocks of kGThreads outputs, strips of kChan channels, clouds)
+template <bool WEIGHTED>
+__global__ __launch_bounds__(kGThreads) void gather_direct_kernel(
+    int c, int n_src, int m_out, const float *__restrict__ points, const int *__restrict__ idx,
+    const float *__restrict__ weight, float *__restrict__ out) {
   const int p = blockIdx.x * kGThreads + threadIdx.x;
-  if (p >= m) return;
+  if (p >= m_out) return;
   const int cloud = blockIdx.z;
   const int c0 = blockIdx.y * kChan;
-  const int id = idx[(size_t)cloud * m + p];
-  const float *src = points + ((size_t)cloud * c + c0) * n + id;
-  float *dst = out + ((size_t)cloud * c + c0) * m + p;
+  const Taps<WEIGHTED> tap(idx, weight, (size_t)cloud * m_out + p);
+  const float *src = points + ((size_t)cloud * c + c0) * n_src;
+  float *dst = out + ((size_t)cloud * c + c0) * m_out + p;
   const int cn = min(kChan, c - c0);
-  if (cn == kChan) {
+  if (!WEIGHTED && cn == kChan) {  // a full strip of copies: all loads in flight before the first store
     float v[kChan];
 #pragma unroll
-    for (int k = 0; k < kChan; ++k) v[k] = src[(size_t)k * n];
+    for (int k = 0; k < kChan; ++k) v[k] = tap.read(src + (size_t)k * n_src);
 #pragma unroll
-    for (int k = 0; k < kChan; ++k) dst[(size_t)k * m] = v[k];
+    for (int k = 0; k < kChan; ++k) dst[(size_t)k * m_out] = v[k];
   } else {
-    for (int k = 0; k < cn; ++k) dst[(size_t)k * m] = src[(size_t)k * n];
+    for (int k = 0; k < cn; ++k) dst[(size_t)k * m_out] = tap.read(src + (size_t)k * n_src);
   }
 }
 
-__global__ __launch_bounds__(kGThreads) void gather_grad_kernel(
-    int c, int n, int m, const float *__restrict__ grad_out,
-    const int *__restrict__ idx, float *__restrict__ grad_points) {
+// The gradient with global atomics (rows too long for the LDS scatter below); same grid over the grad_out columns.
+template <bool WEIGHTED>
+__global__ __launch_bounds__(kGThreads) void scatter_atomic_kernel(
+    int c, int n_dst, int m_src, const float *__restrict__ grad_out, const int *__restrict__ idx,
+    const float *__restrict__ weight, float *__restrict__ grad_points) {
   const int p = blockIdx.x * kGThreads + threadIdx.x;
-  if (p >= m) return;
+  if (p >= m_src) return;
   const int cloud = blockIdx.z;
   const int c0 = blockIdx.y * kChan;
-  const int id = idx[(size_t)cloud * m + p];
-  const float *src = grad_out + ((size_t)cloud * c + c0) * m + p;
-  float *dst = grad_points + ((size_t)cloud * c + c0) * n + id;
+  const Taps<WEIGHTED> tap(idx, weight, (size_t)cloud * m_src + p);
+  const float *src = grad_out + ((size_t)cloud * c + c0) * m_src + p;
+  float *dst = grad_points + ((size_t)cloud * c + c0) * n_dst;
   const int cn = min(kChan, c - c0);
-  for (int k = 0; k < cn; ++k) atomicAdd(dst + (size_t)k * n, src[(size_t)k * m]);
-}
-
-__global__ __launch_bounds__(kGThreads) void three_interpolate_kernel(
-    int c, int m, int n, const float *__restrict__ points,
-    const int *__restrict__ idx, const float *__restrict__ weight,
-    float *__restrict__ out) {
-  const int p = blockIdx.x * kGThreads + threadIdx.x;
-  if (p >= n) return;
-  const int cloud = blockIdx.z;
-  const int c0 = blockIdx.y * kChan;
-  const int *id = idx + ((size_t)cloud * n + p) * 3;
-  const float *w = weight + ((size_t)cloud * n + p) * 3;
-  const int i0 = id[0], i1 = id[1], i2 = id[2];
-  const float w0 = w[0], w1 = w[1], w2 = w[2];
-  const float *src = points + ((size_t)cloud * c + c0) * m;
-  float *dst = out + ((size_t)cloud * c + c0) * n + p;
-  const int cn = min(kChan, c - c0);
-  for (int k = 0; k < cn; ++k) {
-    const float *row = src + (size_t)k * m;
-    // w0*p0 + w1*p1 + w2*p2 == fma(w2,p2, fma(w1,p1, w0*p0)) (oracle chain)
-    dst[(size_t)k * n] =
-        __builtin_fmaf(w2, row[i2], __builtin_fmaf(w1, row[i1], w0 * row[i0]));
-  }
-}
-
-__global__ __launch_bounds__(kGThreads) void three_interpolate_grad_kernel(
-    int c, int n, int m, const float *__restrict__ grad_out,
-    const int *__restrict__ idx, const float *__restrict__ weight,
-    float *__restrict__ grad_points) {
-  const int p = blockIdx.x * kGThreads + threadIdx.x;
-  if (p >= n) return;
-  const int cloud = blockIdx.z;
-  const int c0 = blockIdx.y * kChan;
-  const int *id = idx + ((size_t)cloud * n + p) * 3;
-  const float *w = weight + ((size_t)cloud * n + p) * 3;
-  const int i0 = id[0], i1 = id[1], i2 = id[2];
-  const float w0 = w[0], w1 = w[1], w2 = w[2];
-  const float *src = grad_out + ((size_t)cloud * c + c0) * n + p;
-  float *dst = grad_points + ((size_t)cloud * c + c0) * m;
-  const int cn = min(kChan, c - c0);
-  for (int k = 0; k < cn; ++k) {
-    const float g = src[(size_t)k * n];
-    float *row = dst + (size_t)k * m;
-    atomicAdd(row + i0, g * w0);
-    atomicAdd(row + i1, g * w1);
-    atomicAdd(row + i2, g * w2);
-  }
+  for (int k = 0; k < cn; ++k) tap.add(dst + (size_t)k * n_dst, src[(size_t)k * m_src]);
 }
 
 constexpr int kScThreads = 1024;
 constexpr int kScFloats = 24576;  // 96 KiB of LDS rows / accumulators per workgroup
+
+// The frame of the LDS kernels: grid (strips of `ch` channels, clouds), one workgroup owns rows c0 .. c0 + cn of one
+// cloud, stages or zeroes them in LDS, and writes or adds them back with coalesced stores.
+struct Strip {
+  int c, cloud, c0, cn;
+  __device__ __forceinline__ Strip(int c, int ch) : c(c), cloud(blockIdx.y), c0(blockIdx.x * ch), cn(min(ch, c - c0)) {}
+  // the strip's rows of a (B, C, len) tensor: rows c0.. are contiguous, cn * len elements
+  template <typename T>
+  __device__ __forceinline__ T *rows(T *tensor, int len) const { return tensor + ((size_t)cloud * c + c0) * len; }
+};
+__device__ __forceinline__ void strip_stage(float *lds, const float *__restrict__ src, int count) {
+  for (int i = threadIdx.x; i < count; i += kScThreads) lds[i] = src[i];
+  __syncthreads();
+}
+__device__ __forceinline__ void strip_zero(float *lds, int count) {
+  for (int i = threadIdx.x; i < count; i += kScThreads) lds[i] = 0.f;
+  __syncthreads();
+}
+// OVERWRITE: the rows are written, not accumulated into (nobody else touches them either way)
+template <bool OVERWRITE>
+__device__ __forceinline__ void strip_flush(float *__restrict__ dst, const float *lds, int count) {
+  __syncthreads();
+  for (int i = threadIdx.x; i < count; i += kScThreads) {
+    if constexpr (OVERWRITE) dst[i] = lds[i];
+    else dst[i] += lds[i];
+  }
+}
 
 // Gather through LDS.  The direct kernel reads 4 scattered bytes per output
 // element, i.e. a whole cache sector: with the points of one (cloud, channel)
@@ -122,33 +136,16 @@ template <bool WEIGHTED>
 __global__ __launch_bounds__(kScThreads) void gather_lds_kernel(
     int c, int n_src, int m_out, int ch, const float *__restrict__ points,
     const int *__restrict__ idx, const float *__restrict__ weight, float *__restrict__ out) {
+  constexpr int R = Taps<WEIGHTED>::R;
   __shared__ float rows[kScFloats];
-  const int t = threadIdx.x;
-  const int cloud = blockIdx.y;
-  const int c0 = blockIdx.x * ch;
-  const int cn = min(ch, c - c0);
-  const float *src = points + ((size_t)cloud * c + c0) * n_src;  // rows c0.. are contiguous
-  for (int i = t; i < cn * n_src; i += kScThreads) rows[i] = src[i];
-  __syncthreads();
-  float *dst = out + ((size_t)cloud * c + c0) * m_out;
-  if constexpr (!WEIGHTED) {
-    const int *id = idx + (size_t)cloud * m_out;
-    for (int p = t; p < m_out; p += kScThreads) {
-      const int j = id[p];
-      for (int k = 0; k < cn; ++k) dst[(size_t)k * m_out + p] = rows[k * n_src + j];
-    }
-  } else {
-    const int *id = idx + (size_t)cloud * m_out * 3;
-    const float *w = weight + (size_t)cloud * m_out * 3;
-    for (int p = t; p < m_out; p += kScThreads) {
-      const int i0 = id[p * 3 + 0], i1 = id[p * 3 + 1], i2 = id[p * 3 + 2];
-      const float w0 = w[p * 3 + 0], w1 = w[p * 3 + 1], w2 = w[p * 3 + 2];
-      for (int k = 0; k < cn; ++k) {
-        const float *row = rows + k * n_src;
-        // w0*p0 + w1*p1 + w2*p2 == fma(w2,p2, fma(w1,p1, w0*p0)) (oracle chain)
-        dst[(size_t)k * m_out + p] = __builtin_fmaf(w2, row[i2], __builtin_fmaf(w1, row[i1], w0 * row[i0]));
-      }
-    }
+  const Strip s(c, ch);
+  strip_stage(rows, s.rows(points, n_src), s.cn * n_src);
+  float *dst = s.rows(out, m_out);
+  const int *id = idx + (size_t)s.cloud * m_out * R;
+  const float *w = WEIGHTED ? weight + (size_t)s.cloud * m_out * R : nullptr;
+  for (int p = threadIdx.x; p < m_out; p += kScThreads) {
+    const Taps<WEIGHTED> tap(id, w, p);
+    for (int k = 0; k < s.cn; ++k) dst[(size_t)k * m_out + p] = tap.read(rows + k * n_src);
   }
 }
 
@@ -166,46 +163,28 @@ __global__ __launch_bounds__(kScThreads) void scatter_lds_kernel(
     int c, int n_dst, int m_src, int ch, const float *__restrict__ grad_out,
     const int *__restrict__ idx, const float *__restrict__ weight,
     float *__restrict__ grad_points) {
+  constexpr int R = Taps<WEIGHTED>::R;
   __shared__ float acc[kScFloats];
-  const int t = threadIdx.x;
-  const int cloud = blockIdx.y;
-  const int c0 = blockIdx.x * ch;
-  const int cn = min(ch, c - c0);
-  for (int i = t; i < cn * n_dst; i += kScThreads) acc[i] = 0.f;
-  __syncthreads();
-  const float *src = grad_out + ((size_t)cloud * c + c0) * m_src;
-  if constexpr (!WEIGHTED) {
-    const int *id = idx + (size_t)cloud * m_src;
-    for (int p = t; p < m_src; p += kScThreads) {
-      const int j = id[p];
-      int k = 0;
-      for (; k + 4 <= cn; k += 4) {
-        const float g0 = src[(size_t)(k + 0) * m_src + p], g1 = src[(size_t)(k + 1) * m_src + p];
-        const float g2 = src[(size_t)(k + 2) * m_src + p], g3 = src[(size_t)(k + 3) * m_src + p];
-        atomicAdd(&acc[(k + 0) * n_dst + j], g0);
-        atomicAdd(&acc[(k + 1) * n_dst + j], g1);
-        atomicAdd(&acc[(k + 2) * n_dst + j], g2);
-        atomicAdd(&acc[(k + 3) * n_dst + j], g3);
-      }
-      for (; k < cn; ++k) atomicAdd(&acc[k * n_dst + j], src[(size_t)k * m_src + p]);
-    }
-  } else {
-    const int *id = idx + (size_t)cloud * m_src * 3;
-    const float *w = weight + (size_t)cloud * m_src * 3;
-    for (int p = t; p < m_src; p += kScThreads) {
-      const int i0 = id[p * 3 + 0], i1 = id[p * 3 + 1], i2 = id[p * 3 + 2];
-      const float w0 = w[p * 3 + 0], w1 = w[p * 3 + 1], w2 = w[p * 3 + 2];
-      for (int k = 0; k < cn; ++k) {
-        const float g = src[(size_t)k * m_src + p];
-        atomicAdd(&acc[k * n_dst + i0], g * w0);
-        atomicAdd(&acc[k * n_dst + i1], g * w1);
-        atomicAdd(&acc[k * n_dst + i2], g * w2);
+  const Strip s(c, ch);
+  strip_zero(acc, s.cn * n_dst);
+  const float *src = s.rows(grad_out, m_src);
+  const int *id = idx + (size_t)s.cloud * m_src * R;
+  const float *w = WEIGHTED ? weight + (size_t)s.cloud * m_src * R : nullptr;
+  for (int p = threadIdx.x; p < m_src; p += kScThreads) {
+    const Taps<WEIGHTED> tap(id, w, p);
+    int k = 0;
+    if constexpr (!WEIGHTED) {  // one atomic per row: four rows' loads go out before the first of them
+      for (; k + 4 <= s.cn; k += 4) {
+        float g[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) g[u] = src[(size_t)(k + u) * m_src + p];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) tap.add(acc + (k + u) * n_dst, g[u]);
       }
     }
+    for (; k < s.cn; ++k) tap.add(acc + k * n_dst, src[(size_t)k * m_src + p]);
   }
-  __syncthreads();
-  float *dst = grad_points + ((size_t)cloud * c + c0) * n_dst;  // rows c0.. are contiguous
-  for (int i = t; i < cn * n_dst; i += kScThreads) dst[i] += acc[i];
+  strip_flush<false>(s.rows(grad_points, n_dst), acc, s.cn * n_dst);
 }
 
 // ---------------------------------------------------------------------------
@@ -249,8 +228,8 @@ __global__ __launch_bounds__(kScThreads) void transpose_index_kernel(
     char *__restrict__ scratch) {
   constexpr int R = WEIGHTED ? 3 : 1;
   __shared__ int cnt[kTrMaxDst];
-  __shared__ int wtot[kScThreads / kWave];
-  const int t = threadIdx.x, lane = t & (kWave - 1), wave = t >> 6;
+  __shared__ int s_wsum[kScThreads / kWave];
+  const int t = threadIdx.x;
   const int q = blockIdx.x, cloud = blockIdx.y, nq = gridDim.x;
   const int p0 = q * chunk;
   const int ne = min(chunk, m_src - p0) * R;  // entries of this chunk
@@ -267,17 +246,7 @@ __global__ __launch_bounds__(kScThreads) void transpose_index_kernel(
   const int j0 = t * per;
   int sum = 0;
   for (int i = 0; i < per; ++i) sum += j0 + i < n_dst ? cnt[j0 + i] : 0;
-  int incl = sum;
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    const int o = __shfl_up(incl, d);
-    if (lane >= d) incl += o;
-  }
-  if (lane == kWave - 1) wtot[wave] = incl;
-  __syncthreads();
-  int base = 0;
-  for (int w = 0; w < wave; ++w) base += wtot[w];
-  int run = base + incl - sum;
+  int run = block_exclusive_sum(sum, s_wsum);
   char *base_p = scratch + ((size_t)cloud * nq + q) * tr_chunk_bytes(n_dst, chunk, R);
   tr_u16 *off = reinterpret_cast<tr_u16 *>(base_p);
   for (int i = 0; i < per; ++i) {
@@ -434,17 +403,16 @@ __global__ __launch_bounds__(kScThreads) void gather_max_lds_kernel(
     int c, int n_src, int p_out, int k, int ch, const float *__restrict__ points,
     const int *__restrict__ idx, float *__restrict__ out, int *__restrict__ arg) {
   __shared__ float rows[kScFloats];
-  const int t = threadIdx.x;
-  const int cloud = blockIdx.y;
-  const int c0 = blockIdx.x * ch;
-  const int cn = min(ch, c - c0);
-  const float *src = points + ((size_t)cloud * c + c0) * n_src;  // rows c0.. are contiguous
-  for (int i = t; i < cn * n_src; i += kScThreads) rows[i] = src[i];
+  const Strip s(c, ch);
+  const int cn = s.cn;
+  const float *src = s.rows(points, n_src);
+  // (spelled out: through strip_stage two instructions trade places, and this kernel stays as it was measured)
+  for (int i = threadIdx.x; i < cn * n_src; i += kScThreads) rows[i] = src[i];
   __syncthreads();
-  float *dst = out + ((size_t)cloud * c + c0) * p_out;
-  int *adst = arg + ((size_t)cloud * c + c0) * p_out;
-  const int *id = idx + (size_t)cloud * p_out * k;
-  for (int p = t; p < p_out; p += kScThreads) {
+  float *dst = s.rows(out, p_out);
+  int *adst = s.rows(arg, p_out);
+  const int *id = idx + (size_t)s.cloud * p_out * k;
+  for (int p = threadIdx.x; p < p_out; p += kScThreads) {
     float best[kGmChan];
     int bi[kGmChan];
 #pragma unroll
@@ -489,25 +457,16 @@ __global__ __launch_bounds__(kScThreads) void gather_max_grad_kernel(
     int c, int n_dst, int p_src, int ch, const float *__restrict__ grad_out, const int *__restrict__ arg,
     float *__restrict__ grad_points) {
   __shared__ float acc[kScFloats];
-  const int t = threadIdx.x;
-  const int cloud = blockIdx.y;
-  const int c0 = blockIdx.x * ch;
-  const int cn = min(ch, c - c0);
-  for (int i = t; i < cn * n_dst; i += kScThreads) acc[i] = 0.f;
-  __syncthreads();
-  const float *src = grad_out + ((size_t)cloud * c + c0) * p_src;
-  const int *asrc = arg + ((size_t)cloud * c + c0) * p_src;
-  for (int i = t; i < cn * p_src; i += kScThreads) {   // (row q, point p) = (i / p_src, i % p_src): coalesced
+  const Strip s(c, ch);
+  strip_zero(acc, s.cn * n_dst);
+  const float *src = s.rows(grad_out, p_src);
+  const int *asrc = s.rows(arg, p_src);
+  for (int i = threadIdx.x; i < s.cn * p_src; i += kScThreads) {   // (row q, point p) = (i / p_src, i % p_src): coalesced
     const int q = i / p_src;
     const int j = asrc[i];
     if ((unsigned)j < (unsigned)n_dst) atomicAdd(&acc[q * n_dst + j], src[i]);
   }
-  __syncthreads();
-  float *dst = grad_points + ((size_t)cloud * c + c0) * n_dst;
-  for (int i = t; i < cn * n_dst; i += kScThreads) {
-    if constexpr (OVERWRITE) dst[i] = acc[i];
-    else dst[i] += acc[i];
-  }
+  strip_flush<OVERWRITE>(s.rows(grad_points, n_dst), acc, s.cn * n_dst);
 }
 
 static long long transposed_scratch_bytes(int b, int n_dst, int m_src, int r) {
@@ -558,122 +517,50 @@ static bool grid_ok(long long gx, long long gy, long long gz) {
   return gx <= 2147483647LL && gy <= 65535 && gz <= 65535;
 }
 
-}  // namespace mvp
-
-using namespace mvp;
-
-extern "C" int mvp_gather_points(int b, int c, int n, int npoints,
-                                 const float *points, const int *idx,
-                                 float *out, void *stream) {
-  if (b < 0 || c < 0 || n < 0 || npoints < 0) return MVP_EBADSHAPE;
-  if (b == 0 || c == 0 || npoints == 0) return MVP_OK;
-  if (n == 0) return MVP_EBADSHAPE;
-  if (!points || !idx || !out) return MVP_EBADARG;
+// The bodies of the entry points.  `what` is the name check_launch records; unweighted callers pass weight = nullptr.
+// out (b, c, m_out) gathered from points (b, c, n_src).
+template <bool WEIGHTED>
+static int gather_forward(const char *what, int b, int c, int n_src, int m_out, const float *points, const int *idx,
+                          const float *weight, float *out, void *stream) {
+  if (b < 0 || c < 0 || n_src < 0 || m_out < 0) return MVP_EBADSHAPE;
+  if (b == 0 || c == 0 || m_out == 0) return MVP_OK;
+  if (n_src == 0) return MVP_EBADSHAPE;
+  if (!points || !idx || (WEIGHTED && !weight) || !out) return MVP_EBADARG;
   // rows short enough to stage and enough outputs per row to pay for staging
-  if (const int ch = scatter_channels(c, n); ch > 0 && 2LL * npoints >= n) {
-    dim3 sgrid((c + ch - 1) / ch, b);
-    if (!grid_ok(sgrid.x, sgrid.y, 1)) return MVP_EBADSHAPE;
-    hipLaunchKernelGGL(gather_lds_kernel<false>, sgrid, dim3(kScThreads), 0, as_stream(stream), c, n, npoints,
-                       ch, points, idx, static_cast<const float *>(nullptr), out);
-    return check_launch("mvp_gather_points");
-  }
-  dim3 grid((npoints + kGThreads - 1) / kGThreads, (c + kChan - 1) / kChan, b);
-  if (!grid_ok(grid.x, grid.y, grid.z)) return MVP_EBADSHAPE;
-  hipLaunchKernelGGL(gather_kernel, grid, dim3(kGThreads), 0, as_stream(stream),
-                     c, n, npoints, points, idx, out);
-  return check_launch("mvp_gather_points");
-}
-
-extern "C" int mvp_gather_points_grad(int b, int c, int n, int npoints,
-                                      const float *grad_out, const int *idx,
-                                      float *grad_points, void *stream) {
-  if (b < 0 || c < 0 || n < 0 || npoints < 0) return MVP_EBADSHAPE;
-  if (b == 0 || c == 0 || npoints == 0) return MVP_OK;
-  if (n == 0) return MVP_EBADSHAPE;
-  if (!grad_out || !idx || !grad_points) return MVP_EBADARG;
-  if (const int ch = scatter_channels(c, n)) {
-    dim3 sgrid((c + ch - 1) / ch, b);
-    if (!grid_ok(sgrid.x, sgrid.y, 1)) return MVP_EBADSHAPE;
-    hipLaunchKernelGGL(scatter_lds_kernel<false>, sgrid, dim3(kScThreads), 0, as_stream(stream), c, n,
-                       npoints, ch, grad_out, idx, static_cast<const float *>(nullptr), grad_points);
-    return check_launch("mvp_gather_points_grad");
-  }
-  dim3 grid((npoints + kGThreads - 1) / kGThreads, (c + kChan - 1) / kChan, b);
-  if (!grid_ok(grid.x, grid.y, grid.z)) return MVP_EBADSHAPE;
-  hipLaunchKernelGGL(gather_grad_kernel, grid, dim3(kGThreads), 0,
-                     as_stream(stream), c, n, npoints, grad_out, idx,
-                     grad_points);
-  return check_launch("mvp_gather_points_grad");
-}
-
-extern "C" int mvp_group_points(int b, int c, int n, int npoints, int nsample,
-                                const float *points, const int *idx, float *out,
-                                void *stream) {
-  if (npoints < 0 || nsample < 0) return MVP_EBADSHAPE;
-  const long long flat = (long long)npoints * nsample;
-  if (flat > 2147483647LL) return MVP_EBADSHAPE;
-  return mvp_gather_points(b, c, n, (int)flat, points, idx, out, stream);
-}
-
-extern "C" int mvp_group_points_grad(int b, int c, int n, int npoints,
-                                     int nsample, const float *grad_out,
-                                     const int *idx, float *grad_points,
-                                     void *stream) {
-  if (npoints < 0 || nsample < 0) return MVP_EBADSHAPE;
-  const long long flat = (long long)npoints * nsample;
-  if (flat > 2147483647LL) return MVP_EBADSHAPE;
-  return mvp_gather_points_grad(b, c, n, (int)flat, grad_out, idx, grad_points,
-                                stream);
-}
-
-extern "C" int mvp_three_interpolate(int b, int c, int m, int n,
-                                     const float *points, const int *idx,
-                                     const float *weight, float *out,
-                                     void *stream) {
-  if (b < 0 || c < 0 || m < 0 || n < 0) return MVP_EBADSHAPE;
-  if (b == 0 || c == 0 || n == 0) return MVP_OK;
-  if (m == 0) return MVP_EBADSHAPE;
-  if (!points || !idx || !weight || !out) return MVP_EBADARG;
-  if (const int ch = scatter_channels(c, m); ch > 0 && 2LL * n >= m) {
-    dim3 sgrid((c + ch - 1) / ch, b);
-    if (!grid_ok(sgrid.x, sgrid.y, 1)) return MVP_EBADSHAPE;
-    hipLaunchKernelGGL(gather_lds_kernel<true>, sgrid, dim3(kScThreads), 0, as_stream(stream), c, m, n, ch,
+  if (const int ch = scatter_channels(c, n_src); ch > 0 && 2LL * m_out >= n_src) {
+    dim3 grid((c + ch - 1) / ch, b);
+    if (!grid_ok(grid.x, grid.y, 1)) return MVP_EBADSHAPE;
+    hipLaunchKernelGGL(gather_lds_kernel<WEIGHTED>, grid, dim3(kScThreads), 0, as_stream(stream), c, n_src, m_out, ch,
                        points, idx, weight, out);
-    return check_launch("mvp_three_interpolate");
+  } else {
+    dim3 grid((m_out + kGThreads - 1) / kGThreads, (c + kChan - 1) / kChan, b);
+    if (!grid_ok(grid.x, grid.y, grid.z)) return MVP_EBADSHAPE;
+    hipLaunchKernelGGL(gather_direct_kernel<WEIGHTED>, grid, dim3(kGThreads), 0, as_stream(stream), c, n_src, m_out,
+                       points, idx, weight, out);
   }
-  dim3 grid((n + kGThreads - 1) / kGThreads, (c + kChan - 1) / kChan, b);
-  if (!grid_ok(grid.x, grid.y, grid.z)) return MVP_EBADSHAPE;
-  hipLaunchKernelGGL(three_interpolate_kernel, grid, dim3(kGThreads), 0,
-                     as_stream(stream), c, m, n, points, idx, weight, out);
-  return check_launch("mvp_three_interpolate");
+  return check_launch(what);
 }
 
-extern "C" int mvp_three_interpolate_grad(int b, int c, int n, int m,
-                                          const float *grad_out, const int *idx,
-                                          const float *weight,
-                                          float *grad_points, void *stream) {
-  if (b < 0 || c < 0 || m < 0 || n < 0) return MVP_EBADSHAPE;
-  if (b == 0 || c == 0 || n == 0) return MVP_OK;
-  if (m == 0) return MVP_EBADSHAPE;
-  if (!grad_out || !idx || !weight || !grad_points) return MVP_EBADARG;
-  if (const int ch = scatter_channels(c, m)) {
-    dim3 sgrid((c + ch - 1) / ch, b);
-    if (!grid_ok(sgrid.x, sgrid.y, 1)) return MVP_EBADSHAPE;
-    hipLaunchKernelGGL(scatter_lds_kernel<true>, sgrid, dim3(kScThreads), 0, as_stream(stream), c, m, n,
-                       ch, grad_out, idx, weight, grad_points);
-    return check_launch("mvp_three_interpolate_grad");
+// grad_points (b, c, n_dst) += the scatter of grad_out (b, c, m_src).
+template <bool WEIGHTED>
+static int scatter_backward(const char *what, int b, int c, int n_dst, int m_src, const float *grad_out, const int *idx,
+                            const float *weight, float *grad_points, void *stream) {
+  if (b < 0 || c < 0 || n_dst < 0 || m_src < 0) return MVP_EBADSHAPE;
+  if (b == 0 || c == 0 || m_src == 0) return MVP_OK;
+  if (n_dst == 0) return MVP_EBADSHAPE;
+  if (!grad_out || !idx || (WEIGHTED && !weight) || !grad_points) return MVP_EBADARG;
+  if (const int ch = scatter_channels(c, n_dst)) {
+    dim3 grid((c + ch - 1) / ch, b);
+    if (!grid_ok(grid.x, grid.y, 1)) return MVP_EBADSHAPE;
+    hipLaunchKernelGGL(scatter_lds_kernel<WEIGHTED>, grid, dim3(kScThreads), 0, as_stream(stream), c, n_dst, m_src, ch,
+                       grad_out, idx, weight, grad_points);
+  } else {
+    dim3 grid((m_src + kGThreads - 1) / kGThreads, (c + kChan - 1) / kChan, b);
+    if (!grid_ok(grid.x, grid.y, grid.z)) return MVP_EBADSHAPE;
+    hipLaunchKernelGGL(scatter_atomic_kernel<WEIGHTED>, grid, dim3(kGThreads), 0, as_stream(stream), c, n_dst, m_src,
+                       grad_out, idx, weight, grad_points);
   }
-  dim3 grid((n + kGThreads - 1) / kGThreads, (c + kChan - 1) / kChan, b);
-  if (!grid_ok(grid.x, grid.y, grid.z)) return MVP_EBADSHAPE;
-  hipLaunchKernelGGL(three_interpolate_grad_kernel, grid, dim3(kGThreads), 0,
-                     as_stream(stream), c, n, m, grad_out, idx, weight,
-                     grad_points);
-  return check_launch("mvp_three_interpolate_grad");
-}
-
-// ---- gradients with caller-provided scratch (transposed index list)
-extern "C" long long mvp_scatter_scratch_bytes(int b, int n_dst, int m_src, int r) {
-  return transposed_scratch_bytes(b, n_dst, m_src, r);
+  return check_launch(what);
 }
 
 // The plain kernels accumulate: an overwrite request that falls back to them zero-fills first.
@@ -685,49 +572,97 @@ static int zero_for_overwrite(int mode, float *grad_points, long long count, voi
   return MVP_OK;
 }
 
+// The same with caller-provided scratch (transposed index list); without enough of it, the plain entry (`what_plain`).
+template <bool WEIGHTED>
+static int scatter_backward_ws(const char *what, const char *what_plain, int b, int c, int n_dst, int m_src,
+                               const float *grad_out, const int *idx, const float *weight, float *grad_points,
+                               void *scratch, long long scratch_bytes, int mode, void *stream) {
+  if (b < 0 || c < 0 || n_dst < 0 || m_src < 0) return MVP_EBADSHAPE;
+  const long long need = transposed_scratch_bytes(b, n_dst, m_src, WEIGHTED ? 3 : 1);
+  if (c == 0 || m_src == 0 || !scratch || need == 0 || scratch_bytes < need) {
+    if (const int rc = zero_for_overwrite(mode, grad_points, (long long)b * c * n_dst, stream)) return rc;
+    return scatter_backward<WEIGHTED>(what_plain, b, c, n_dst, m_src, grad_out, idx, weight, grad_points, stream);
+  }
+  if (!grad_out || !idx || (WEIGHTED && !weight) || !grad_points) return MVP_EBADARG;
+  transposed_scatter<WEIGHTED>(b, c, n_dst, m_src, grad_out, idx, weight, grad_points, scratch, mode, as_stream(stream));
+  return check_launch(what);
+}
+
+// grouping_operation: the (npoint, nsample) index array flattened; -1 (refused as a bad shape) when either is negative
+// or the product does not fit an int
+static int flat_count(int npoints, int nsample) {
+  const long long flat = (long long)npoints * nsample;
+  return npoints < 0 || nsample < 0 || flat > 2147483647LL ? -1 : (int)flat;
+}
+
+}  // namespace mvp
+
+using namespace mvp;
+
+extern "C" int mvp_gather_points(int b, int c, int n, int npoints, const float *points, const int *idx, float *out,
+                                 void *stream) {
+  return gather_forward<false>("mvp_gather_points", b, c, n, npoints, points, idx, nullptr, out, stream);
+}
+
+extern "C" int mvp_gather_points_grad(int b, int c, int n, int npoints, const float *grad_out, const int *idx,
+                                      float *grad_points, void *stream) {
+  return scatter_backward<false>("mvp_gather_points_grad", b, c, n, npoints, grad_out, idx, nullptr, grad_points, stream);
+}
+
+extern "C" int mvp_group_points(int b, int c, int n, int npoints, int nsample, const float *points, const int *idx,
+                                float *out, void *stream) {
+  return gather_forward<false>("mvp_gather_points", b, c, n, flat_count(npoints, nsample), points, idx, nullptr, out, stream);
+}
+
+extern "C" int mvp_group_points_grad(int b, int c, int n, int npoints, int nsample, const float *grad_out,
+                                     const int *idx, float *grad_points, void *stream) {
+  return scatter_backward<false>("mvp_gather_points_grad", b, c, n, flat_count(npoints, nsample), grad_out, idx, nullptr,
+                                 grad_points, stream);
+}
+
+// (m source points, n outputs)
+extern "C" int mvp_three_interpolate(int b, int c, int m, int n, const float *points, const int *idx,
+                                     const float *weight, float *out, void *stream) {
+  return gather_forward<true>("mvp_three_interpolate", b, c, m, n, points, idx, weight, out, stream);
+}
+
+extern "C" int mvp_three_interpolate_grad(int b, int c, int n, int m, const float *grad_out, const int *idx,
+                                          const float *weight, float *grad_points, void *stream) {
+  return scatter_backward<true>("mvp_three_interpolate_grad", b, c, m, n, grad_out, idx, weight, grad_points, stream);
+}
+
+// ---- gradients with caller-provided scratch (transposed index list)
+extern "C" long long mvp_scatter_scratch_bytes(int b, int n_dst, int m_src, int r) {
+  return transposed_scratch_bytes(b, n_dst, m_src, r);
+}
+
 extern "C" int mvp_gather_points_grad_ws(int b, int c, int n, int npoints, const float *grad_out, const int *idx,
                                          float *grad_points, void *scratch, long long scratch_bytes, int mode,
                                          void *stream) {
-  if (b < 0 || c < 0 || n < 0 || npoints < 0) return MVP_EBADSHAPE;
-  const long long need = transposed_scratch_bytes(b, n, npoints, 1);
-  if (c == 0 || npoints == 0 || !scratch || need == 0 || scratch_bytes < need) {
-    if (const int rc = zero_for_overwrite(mode, grad_points, (long long)b * c * n, stream)) return rc;
-    return mvp_gather_points_grad(b, c, n, npoints, grad_out, idx, grad_points, stream);
-  }
-  if (!grad_out || !idx || !grad_points) return MVP_EBADARG;
-  transposed_scatter<false>(b, c, n, npoints, grad_out, idx, nullptr, grad_points, scratch, mode, as_stream(stream));
-  return check_launch("mvp_gather_points_grad_ws");
+  return scatter_backward_ws<false>("mvp_gather_points_grad_ws", "mvp_gather_points_grad", b, c, n, npoints, grad_out, idx,
+                                    nullptr, grad_points, scratch, scratch_bytes, mode, stream);
 }
 
 extern "C" int mvp_group_points_grad_ws(int b, int c, int n, int npoints, int nsample, const float *grad_out,
                                         const int *idx, float *grad_points, void *scratch,
                                         long long scratch_bytes, int mode, void *stream) {
-  if (npoints < 0 || nsample < 0) return MVP_EBADSHAPE;
-  const long long flat = (long long)npoints * nsample;
-  if (flat > 2147483647LL) return MVP_EBADSHAPE;
-  return mvp_gather_points_grad_ws(b, c, n, (int)flat, grad_out, idx, grad_points, scratch, scratch_bytes, mode,
-                                   stream);
+  return scatter_backward_ws<false>("mvp_gather_points_grad_ws", "mvp_gather_points_grad", b, c, n,
+                                    flat_count(npoints, nsample), grad_out, idx, nullptr, grad_points, scratch,
+                                    scratch_bytes, mode, stream);
 }
 
 extern "C" int mvp_three_interpolate_grad_ws(int b, int c, int n, int m, const float *grad_out, const int *idx,
                                              const float *weight, float *grad_points, void *scratch,
                                              long long scratch_bytes, int mode, void *stream) {
-  if (b < 0 || c < 0 || m < 0 || n < 0) return MVP_EBADSHAPE;
-  const long long need = transposed_scratch_bytes(b, m, n, 3);
-  if (c == 0 || n == 0 || !scratch || need == 0 || scratch_bytes < need) {
-    if (const int rc = zero_for_overwrite(mode, grad_points, (long long)b * c * m, stream)) return rc;
-    return mvp_three_interpolate_grad(b, c, n, m, grad_out, idx, weight, grad_points, stream);
-  }
-  if (!grad_out || !idx || !weight || !grad_points) return MVP_EBADARG;
-  transposed_scatter<true>(b, c, m, n, grad_out, idx, weight, grad_points, scratch, mode, as_stream(stream));
-  return check_launch("mvp_three_interpolate_grad_ws");
+  return scatter_backward_ws<true>("mvp_three_interpolate_grad_ws", "mvp_three_interpolate_grad", b, c, m, n, grad_out,
+                                   idx, weight, grad_points, scratch, scratch_bytes, mode, stream);
 }
 
 extern "C" int mvp_gather_max(int b, int c, int n, int npoints, int k, const float *points, const int *idx,
                               float *out, int *arg, void *stream) {
   if (b < 0 || c < 0 || n < 0 || npoints < 0 || k <= 0) return MVP_EBADSHAPE;
   if (b == 0 || c == 0 || npoints == 0) return MVP_OK;
-  if (n == 0 || b > 65535) return MVP_EBADSHAPE;
+  if (n == 0) return MVP_EBADSHAPE;
   if (!points || !idx || !out || !arg) return MVP_EBADARG;
   const int ch = min(scatter_channels(c, n), kGmChan);
   if (ch <= 0) return MVP_EBADSHAPE;   // rows longer than the LDS staging buffer: the caller gathers + reduces
@@ -742,17 +677,12 @@ extern "C" int mvp_gather_max_grad(int b, int c, int n, int npoints, const float
                                    float *grad_points, int overwrite, void *stream) {
   if (b < 0 || c < 0 || n < 0 || npoints < 0) return MVP_EBADSHAPE;
   if (b == 0 || c == 0 || n == 0) return MVP_OK;
-  if (b > 65535) return MVP_EBADSHAPE;
   if (!grad_out || !arg || !grad_points) return MVP_EBADARG;
   const int ch = scatter_channels(c, n);
   if (ch <= 0) return MVP_EBADSHAPE;
   dim3 grid((c + ch - 1) / ch, b);
   if (!grid_ok(grid.x, grid.y, 1)) return MVP_EBADSHAPE;
-  if (overwrite)
-    hipLaunchKernelGGL(gather_max_grad_kernel<true>, grid, dim3(kScThreads), 0, as_stream(stream), c, n, npoints, ch,
-                       grad_out, arg, grad_points);
-  else
-    hipLaunchKernelGGL(gather_max_grad_kernel<false>, grid, dim3(kScThreads), 0, as_stream(stream), c, n, npoints, ch,
-                       grad_out, arg, grad_points);
+  hipLaunchKernelGGL(overwrite ? gather_max_grad_kernel<true> : gather_max_grad_kernel<false>, grid, dim3(kScThreads), 0,
+                     as_stream(stream), c, n, npoints, ch, grad_out, arg, grad_points);
   return check_launch("mvp_gather_max_grad");
 }

@@ -95,6 +95,20 @@ def _scatter_commit(key, idx, weight, scratch):
             _TRANSPOSED.pop(0)
 
 
+def _scatter_grad(entry, grad_out, idx, weight, n_dst, m_src, *dims):
+    """The backward of every gather: grad (B, C, n_dst) = grad_out (B, C, ...: m_src columns per row) scatter-added
+    along idx (weight: the three taps' weights, or None) by the *_grad_ws entry point `entry`, whose dimensions after
+    (B, C) are `dims`.  Written, not accumulated into (OVERWRITE); the inverted list the call builds is published only
+    after it returned."""
+    B, C = grad_out.shape[:2]
+    grad = _new(grad_out, B, C, n_dst)
+    scratch, nbytes, mode, key = _scatter_scratch(idx, weight, B, n_dst, m_src, 1 if weight is None else 3)
+    tensors = (grad_out, idx) if weight is None else (grad_out, idx, weight)
+    call(entry, grad_out.device, B, C, *dims, *tensors, grad, scratch, nbytes, mode)
+    _scatter_commit(key, idx, weight, scratch)
+    return grad
+
+
 # ------------------------------------------------------------------ sampling
 FPS_SORTED_MIN_N = 8193      # clouds of at least this many points (<= 16384) take the Morton-sorted kernel (csrc/fps.hip)
 
@@ -242,13 +256,8 @@ class ThreeInterpolate(Function):
     @staticmethod
     def backward(ctx, grad_out):
         idx, weight, m = ctx.three_interpolate_for_backward
-        B, c, n = grad_out.shape
-        grad_features = _new(grad_out, B, c, m)          # written, not accumulated into (OVERWRITE)
-        scratch, nbytes, mode, key = _scatter_scratch(idx, weight, B, m, n, 3)
-        call("mvp_three_interpolate_grad_ws", grad_out.device, B, c, n, m, grad_out.data.contiguous(), idx, weight,
-             grad_features, scratch, nbytes, mode)
-        _scatter_commit(key, idx, weight, scratch)
-        return grad_features, None, None
+        n = grad_out.shape[2]
+        return _scatter_grad("mvp_three_interpolate_grad_ws", grad_out.data.contiguous(), idx, weight, m, n, n, m), None, None
 
 
 class GatherPoints(Function):
@@ -270,13 +279,8 @@ class GatherPoints(Function):
     @staticmethod
     def backward(ctx, grad_out):
         idx, C, N = ctx.for_backwards
-        B, npoint = idx.shape
-        grad_features = _new(grad_out, B, C, N)
-        scratch, nbytes, mode, key = _scatter_scratch(idx, None, B, N, npoint, 1)
-        call("mvp_gather_points_grad_ws", grad_out.device, B, C, N, npoint, grad_out.data.contiguous(), idx,
-             grad_features, scratch, nbytes, mode)
-        _scatter_commit(key, idx, None, scratch)
-        return grad_features, None
+        npoint = idx.shape[1]
+        return _scatter_grad("mvp_gather_points_grad_ws", grad_out.data.contiguous(), idx, None, N, npoint, N, npoint), None
 
 
 class GroupingOperation(Function):
@@ -297,13 +301,9 @@ class GroupingOperation(Function):
     @staticmethod
     def backward(ctx, grad_out):
         idx, N = ctx.for_backwards
-        B, C, npoint, nsample = grad_out.shape
-        grad_features = _new(grad_out, B, C, N)
-        scratch, nbytes, mode, key = _scatter_scratch(idx, None, B, N, npoint * nsample, 1)
-        call("mvp_group_points_grad_ws", grad_out.device, B, C, N, npoint, nsample, grad_out.data.contiguous(), idx,
-             grad_features, scratch, nbytes, mode)
-        _scatter_commit(key, idx, None, scratch)
-        return grad_features, None
+        npoint, nsample = grad_out.shape[2:]
+        return _scatter_grad("mvp_group_points_grad_ws", grad_out.data.contiguous(), idx, None, N, npoint * nsample,
+                             N, npoint, nsample), None
 
 
 class GatherMax(Function):
@@ -432,18 +432,14 @@ class ShareGatherSum(Function):
         C, n_src = v.shape[1], v.shape[2]
         share = C // max(Cw, 1)
         grad_w = torch.empty_like(w)
-        grad_v = _new(v, B, C, n_src)
         if k == 0:
-            return grad_w, grad_v.zero_(), None
+            return grad_w, _new(v, B, C, n_src, zero=True), None
         grad_vals = _new(v, B, C, k, N)
         call("mvp_share_gather_sum_grad", v.device, B, share, Cw, k, n_src, N, w, v, idx, grad_out.data.contiguous(),
              grad_w, grad_vals)
         if not ctx.needs_input_grad[1]:          # (frozen values: no scatter pass)
             return grad_w, None, None
-        scratch, nbytes, mode, key = _scatter_scratch(idx, None, B, n_src, k * N, 1)
-        call("mvp_group_points_grad_ws", v.device, B, C, n_src, k, N, grad_vals, idx, grad_v, scratch, nbytes, mode)
-        _scatter_commit(key, idx, None, scratch)
-        return grad_w, grad_v, None
+        return grad_w, _scatter_grad("mvp_group_points_grad_ws", grad_vals, idx, None, n_src, k * N, n_src, k, N), None
 
 
 class DenseEdgeConv(Function):
@@ -499,12 +495,7 @@ class DenseEdgeConv(Function):
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
         call("mvp_dense_edge_conv_grad", a.device, B, g, layers, k, N, a, nb_rows, idx, ctr, w, arg,
              grad_out.data.contiguous(), grad_a, grad_edge, grad_ctr, grad_w, scratch, nbytes)
-        grad_nb = None
-        if need_nb:
-            grad_nb = _new(a, B, g, N)
-            scatter, sbytes, mode, key = _scatter_scratch(idx, None, B, N, k * N, 1)
-            call("mvp_group_points_grad_ws", a.device, B, g, N, k, N, grad_edge, idx, grad_nb, scatter, sbytes, mode)
-            _scatter_commit(key, idx, None, scatter)
+        grad_nb = _scatter_grad("mvp_group_points_grad_ws", grad_edge, idx, None, N, k * N, N, k, N) if need_nb else None
         return (grad_a if need_a else None, grad_nb, None, grad_ctr if need_ctr else None, grad_w if need_w else None)
 
 

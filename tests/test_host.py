@@ -113,6 +113,93 @@ def test_guards_and_scratch_sizes_of_the_widened_entry_points():
     assert lib.mvp_furthest_point_sampling_sorted(1, 0, 4, null, null, null, null, 0, null) == -1
 
 
+def test_return_codes_of_the_gather_and_scatter_entry_points():
+    """The nine entry points of csrc/pn2_gather.hip that share one body: which guard answers, and in which order.  Every
+    row returns before a launch (null pointers, or dummy ones behind a guard that refuses first).  Dimensions are given
+    as (b, c, row, count): `row` the length of a feature row (source of a gather, destination of a scatter), `count` the
+    number of outputs / of grad_out columns."""
+    from mvp_benchmark_amd import _lib
+    lib = _lib.load()
+    OK, EBADSHAPE, EBADARG = 0, -1, -2
+    null, dummy = ctypes.c_void_p(0), ctypes.c_void_p(4096)
+    same = lambda b, c, row, count: (b, c, row, count)
+    grouped = lambda b, c, row, count: (b, c, row, count, 1)
+    # name -> (argument order of the dimensions, device pointers, taps per entry of its scratch size or None)
+    entries = {
+        "mvp_gather_points": (same, 3, None), "mvp_gather_points_grad": (same, 3, None),
+        "mvp_group_points": (grouped, 3, None), "mvp_group_points_grad": (grouped, 3, None),
+        "mvp_three_interpolate": (same, 4, None),
+        "mvp_three_interpolate_grad": (lambda b, c, row, count: (b, c, count, row), 4, None),
+        "mvp_gather_points_grad_ws": (same, 3, 1), "mvp_group_points_grad_ws": (grouped, 3, 1),
+        "mvp_three_interpolate_grad_ws": (lambda b, c, row, count: (b, c, count, row), 4, 3),
+    }
+    assert all(name in _lib.SIGNATURES for name in entries)
+    # (b, c, row, count), pointers, code.  "dummy" rows pass every argument guard and are refused by the grid check.
+    table = [
+        ((-1, 3, 8, 8), null, EBADSHAPE), ((1, -1, 8, 8), null, EBADSHAPE), ((1, 3, -1, 8), null, EBADSHAPE),
+        ((1, 3, 8, -1), null, EBADSHAPE),
+        ((-1, 0, 8, 8), null, EBADSHAPE), ((0, 3, 8, -1), null, EBADSHAPE),          # the sign guard comes first
+        ((0, 3, 8, 8), null, OK), ((1, 0, 8, 8), null, OK), ((1, 3, 8, 0), null, OK),  # nothing to do
+        ((1, 3, 0, 0), null, OK), ((0, 0, 0, 0), null, OK),                           # ... also with an empty source
+        ((1, 3, 0, 8), null, EBADSHAPE), ((1, 3, 0, 8), dummy, EBADSHAPE),            # an empty source with work to do
+        ((1, 3, 8, 8), null, EBADARG), ((1, 3, 24577, 8), null, EBADARG), ((65536, 3, 8, 8), null, EBADARG),
+        ((65536, 1, 8, 8), dummy, EBADSHAPE),         # b == 65536 on the LDS routes ...
+        ((65536, 1, 8, 1), dummy, EBADSHAPE),         # ... the direct gather (2 * count < row) ...
+        ((65536, 1, 24577, 1), dummy, EBADSHAPE),     # ... and with rows too long for LDS
+    ]
+
+    def run(name, dims, ptrs, ws=()):
+        order, nptr, _ = entries[name]
+        ptrs = list(ptrs) if isinstance(ptrs, (list, tuple)) else [ptrs] * nptr
+        return getattr(lib, name)(*order(*dims), *ptrs, *ws, null)
+
+    def scratch_need(name, dims):
+        b, _, row, count = dims
+        return _lib.scatter_scratch_bytes(b, row, count, entries[name][2]) if min(dims) >= 0 else 0
+
+    for name, (_, nptr, taps) in entries.items():
+        for dims, ptrs, code in table:
+            if taps is None:
+                assert run(name, dims, ptrs) == code, (name, dims)
+                continue
+            # _ws with no scratch, or with fewer bytes than needed: the plain entry's code
+            plain = run(name[:-3], dims, ptrs)
+            need = scratch_need(name, dims)
+            assert plain == code and run(name, dims, ptrs, (null, 0, 0)) == code, (name, dims)
+            assert run(name, dims, ptrs, (dummy, max(need - 1, 0), 0)) == code, (name, dims, need)
+            if ptrs is null:                                   # ... and with enough of it, the same guards (null buffers)
+                assert run(name, dims, ptrs, (dummy, need, 0)) == code, (name, dims, need)
+        for missing in range(nptr):                            # each required pointer on its own
+            ptrs = [null if i == missing else dummy for i in range(nptr)]
+            if taps is None:
+                assert run(name, (1, 3, 8, 8), ptrs) == EBADARG, (name, missing)
+            else:
+                need = scratch_need(name, (1, 3, 8, 8))
+                assert need > 0
+                assert run(name, (1, 3, 8, 8), ptrs, (null, 0, 0)) == EBADARG, (name, missing)
+                assert run(name, (1, 3, 8, 8), ptrs, (dummy, need, 0)) == EBADARG, (name, missing)
+    # the flattened group: npoint * nsample has to fit an int, whatever else is asked
+    for name in ("mvp_group_points", "mvp_group_points_grad", "mvp_group_points_grad_ws"):
+        ws = (null, 0, 0) if name.endswith("_ws") else ()
+        fn = getattr(lib, name)
+        assert fn(1, 3, 8, 65536, 32768, null, null, null, *ws, null) == EBADSHAPE          # 2^31
+        assert fn(0, 3, 8, 65536, 32768, null, null, null, *ws, null) == EBADSHAPE          # ... in front of the empty batch
+        assert fn(0, 3, 8, 65536, 32767, null, null, null, *ws, null) == OK                 # 2^31 - 32768
+        assert fn(1, 3, 8, 65536, 32767, null, null, null, *ws, null) == EBADARG
+        assert fn(1, 3, 8, 8, -1, null, null, null, *ws, null) == EBADSHAPE
+        assert fn(0, 3, 8, -1, -1, null, null, null, *ws, null) == EBADSHAPE                # (a positive product)
+        assert fn(1, 3, 8, 8, 0, null, null, null, *ws, null) == OK
+    # OVERWRITE has a destination to zero or to write, scratch or not
+    for name, (_, nptr, taps) in entries.items():
+        if taps is not None:
+            ptrs = [dummy] * (nptr - 1) + [null]
+            need = scratch_need(name, (1, 3, 8, 8))
+            for ws in ((null, 0, 1), (dummy, need - 1, 1), (dummy, need, 1), (dummy, need, 3)):
+                assert run(name, (1, 3, 8, 8), ptrs, ws) == EBADARG, (name, ws)
+            assert run(name, (1, 3, 24577, 8), ptrs, (dummy, 1 << 20, 1)) == EBADARG, name   # no scratch size: the fall-back
+            assert run(name, (1, 0, 8, 8), null, (null, 0, 1)) == OK, name                   # nothing to zero
+
+
 def test_operator_surface_matches_reference_names():
     import mvp_benchmark_amd.metrics as metrics
     import mvp_benchmark_amd.mm3d_pn2 as pn2

@@ -65,8 +65,8 @@ for name, fn in (("forward", fwd), ("forward + backward", fwd_bwd)):
     def share(*subs):
         return sum(r[1] for r in rows if any(s in r[0] for s in subs))
     knn = share("knn_kernel")
-    gather = share("gather_lds_kernel", "gather_kernel", "group_points")
-    scatter = share("scatter_lds_kernel", "transposed_reduce_kernel", "transpose_index_kernel", "_grad_kernel")
+    gather = share("gather_lds_kernel", "gather_direct_kernel", "group_points")
+    scatter = share("scatter_lds_kernel", "scatter_atomic_kernel", "transposed_reduce_kernel", "transpose_index_kernel", "_grad_kernel")
     svd = share("svd3")
     print("  %s: GPU time %.2f ms per step = kNN graph %.2f + neighbour gather %.2f + gather gradient %.2f + "
           "Kabsch SVD3 %.3f + everything else (library GEMMs / attention / elementwise) %.2f" % (
