@@ -43,7 +43,7 @@ extern "C" {
 #define MVP_ELAUNCH (-3)
 
 /* ABI version of this header; bumped on any signature change. */
-#define MVP_ABI_VERSION 21
+#define MVP_ABI_VERSION 22
 int mvp_abi_version(void);
 
 /* hipGetErrorString of the last launch failure seen on the calling thread
@@ -487,6 +487,27 @@ int mvp_dense_edge_conv_grad(int b, int g, int layers, int k, int n, const float
                              const int *idx, const float *ctr, const float *w, const int *arg,
                              const float *grad_out, float *grad_a, float *grad_edge, float *grad_ctr,
                              float *grad_w, void *scratch, long long scratch_bytes, void *stream);
+
+/* ABI 22.  DGCNN's edge MLP in inference (registration/models/dcp.py: DGCNN; the reference, dcp.py:286-318, runs conv /
+ * BatchNorm / ReLU / max op by op on (B, C, N, k) tensors): the neighbourhood gather, `stages` 1x1 convolutions each
+ * followed by a per-channel affine map (BatchNorm with its running statistics) and ReLU, and the max over the k
+ * neighbours after every stage, in one kernel -- no (b, C, k, n) tensor exists in global memory.  Per cloud, point p,
+ * slot j:
+ *   e_0[:, j] = [x[:, idx[j, p]] ; x[:, p]]                        (neighbour first, then centre)
+ *   e_i[:, j] = relu(scale_i * (W_i e_{i-1}[:, j]) + shift_i)      i = 1 .. stages
+ *   out[off_i : off_i + w_i, p] = max_j e_i[:, j]                  off_i = w_1 + .. + w_{i-1}
+ * x (b,c,n), idx (b,k,n) int32 k-major (the knn operator's layout; values in [0,n), clamped into it), w: W_1 (w1, 2c),
+ * W_2 (w2, w1), .. row-major, packed back to back, 16-byte aligned; scale, shift (w1 + .. + w_stages); out
+ * (b, w1 + .. + w_stages, n), fully overwritten.
+ * Shapes: stages 1..4 with the unused widths 0, every used width a multiple of 32 in [32, 256], c 1..4, k 1..64,
+ * b <= 65535, n * k < 2^31; anything else is MVP_EBADSHAPE (before the null checks); b == 0 or n == 0 does nothing.
+ * Arithmetic: W_1 e_0 is an fmaf chain over ascending input channels on the vector ALU, W_i e_{i-1} for i >= 2 runs on
+ * v_mfma_f32_32x32x2_f32 (float32 in, float32 accumulate, a k-ordered fmaf chain); the affine map is one fmaf.
+ * Non-finite values, as mvp_pointwise_mfma: relu(t) is the select t < 0 ? 0 : t (a NaN stays a NaN), the maximum is NaN
+ * if a member is (torch.max).  No scratch, no atomics: the same bits on every run.  Forward only. */
+int mvp_edge_mlp_max(int b, int c, int n, int k, int stages, int w1, int w2, int w3, int w4,
+                     const float *x, const int *idx, const float *w, const float *scale,
+                     const float *shift, float *out, void *stream);
 
 /* ------------------------------------------- grouped-feature MLP on MFMA */
 

@@ -51,6 +51,7 @@ SIGNATURES = {
     "mvp_share_gather_sum_grad": "iiiiiipppppp",
     "mvp_dense_edge_conv": "iiiiippppppp",
     "mvp_dense_edge_conv_grad": "iiiiippppppppppppq",
+    "mvp_edge_mlp_max": "iiiiiiiiipppppp",
     "mvp_pointwise_wgrad": "iiiipppppq",
     "mvp_pointwise_dgrad": "iiiippp",
     "mvp_kabsch_svd3": "ipppppp",
@@ -68,7 +69,7 @@ SIGNATURES = {
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "f": ctypes.c_float,
        "q": ctypes.c_longlong}
 
-ABI_VERSION = 21  # MVP_ABI_VERSION of include/mvpops.h this binding was written against
+ABI_VERSION = 22  # MVP_ABI_VERSION of include/mvpops.h this binding was written against
 
 # default of mvp_emd_configure's `split` knob (csrc/emd.hip: emd_knobs)
 EMD_DEFAULT_SPLIT = 5

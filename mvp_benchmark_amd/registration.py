@@ -245,3 +245,56 @@ def gmm_register(pi_s, mu_s, mu_t, sigma_t):
     t = c_t.transpose(1, 2) - R @ c_s.transpose(1, 2)
     bottom = R.new_tensor([0.0, 0.0, 0.0, 1.0]).expand(R.shape[0], 1, 4)
     return torch.cat([torch.cat([R, t], dim=2), bottom], dim=1)
+
+
+# ------------------------------------------------------------------------------------------- DGCNN's edge MLP (DCP)
+# registration/models/dcp.py: DGCNN in inference -- the neighbourhood gather, the 1x1 convolutions with BatchNorm's affine
+# map and ReLU, and the max over the k neighbours after each, as one kernel (mvp_edge_mlp_max, csrc/edge_mlp.hip).
+
+EDGE_MLP = False           # True: DGCNN.forward takes the fused route in eval mode (float32 CUDA, nothing requires grad)
+
+
+def _edge_mlp_reference(x, idx, weights, scales, shifts):
+    """The composition mvp_edge_mlp_max computes, in torch: an explicit gather, then per stage the product with W_i, the
+    affine map, ReLU and the max over k."""
+    B, c, N = x.shape
+    k = idx.shape[1]
+    flat = idx.long().reshape(B, 1, k * N).expand(B, c, k * N)
+    edge = torch.cat((torch.gather(x, 2, flat).reshape(B, c, k, N), x.unsqueeze(2).expand(-1, -1, k, -1)), dim=1)
+    pooled = []
+    for W, sc, sh in zip(weights, scales, shifts):
+        edge = torch.relu(torch.einsum("oc,bckn->bokn", W, edge) * sc.view(1, -1, 1, 1) + sh.view(1, -1, 1, 1))
+        pooled.append(edge.max(dim=2)[0])
+    return torch.cat(pooled, dim=1)
+
+
+def edge_mlp_max(x, idx, weights, scales, shifts):
+    """x (B,c,N) point features, idx (B,k,N) neighbour lists (the knn operator's layout, values in [0,N)), per stage i a
+    weight (w_i, K_i) with K_1 = 2c and K_i = w_{i-1} (a 1x1 convolution's 4-D weight is taken as its matrix), a scale
+    and a shift (w_i) -> (B, w_1 + .. + w_s, N):
+        e_0 = [x[:, idx] ; x],  e_i = relu(scale_i * (W_i e_{i-1}) + shift_i),  out_i = max over k of e_i.
+    float32 CUDA tensors run mvp_edge_mlp_max (1..4 stages, widths multiples of 32 up to 256, c <= 4, k <= 64); CPU /
+    float64 tensors take the same composition written in torch.  ReLU keeps a NaN, the maximum is NaN if a member is.
+    Forward only: no input may require grad while grad mode is on."""
+    weights = [W.reshape(W.shape[0], -1) for W in weights]
+    tensors = [x] + weights + list(scales) + list(shifts)
+    assert not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors)), "edge_mlp_max has no backward"
+    assert x.dim() == 3 and idx.dim() == 3 and idx.shape[0] == x.shape[0] and idx.shape[2] == x.shape[2]
+    assert len(weights) == len(scales) == len(shifts) >= 1
+    fan_in = 2 * x.shape[1]
+    for W, sc, sh in zip(weights, scales, shifts):
+        assert W.shape[1] == fan_in and sc.shape == sh.shape == (W.shape[0],), "stage shapes do not chain"
+        fan_in = W.shape[0]
+    if not _on_op_layer(x):
+        return _edge_mlp_reference(x, idx, weights, scales, shifts)
+    assert len(weights) <= 4, "mvp_edge_mlp_max takes at most four stages"
+    B, c, N = x.shape
+    k = idx.shape[1]
+    widths = [W.shape[0] for W in weights] + [0] * (4 - len(weights))
+    w = torch.cat([W.detach().reshape(-1) for W in weights]).float().contiguous()
+    scale = torch.cat([s.detach() for s in scales]).float().contiguous()
+    shift = torch.cat([s.detach() for s in shifts]).float().contiguous()
+    out = torch.empty(B, sum(widths), N, device=x.device, dtype=torch.float32)
+    call("mvp_edge_mlp_max", x.device, B, c, N, k, len(weights), *widths, x.detach().contiguous(),
+         idx.int().contiguous(), w, scale, shift, out)
+    return out

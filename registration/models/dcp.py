@@ -10,7 +10,9 @@ stages are a loop.  On the op layer: DGCNN's k = 20 coordinate kNN and
 neighbour gather (knn + grouping operators instead of a (B,N,N) matrix, topk and
 advanced indexing) and the SVD head (one mvp_kabsch_svd3 launch instead of B
 torch.svd / torch.det calls with a host synchronisation each).  Attention and
-the 1x1 convolutions are library GEMMs.
+the 1x1 convolutions are library GEMMs -- except on DGCNN's opt-in inference route
+(mvp_benchmark_amd.registration.EDGE_MLP), which runs the four edge stages and their
+maxima as one kernel and conv5 as one MFMA GEMM.
 """
 import copy
 import math
@@ -43,6 +45,7 @@ def _sibling(name):
 _mu = _sibling("model_utils")
 get_graph_feature, procrustes = _mu.get_graph_feature, _mu.procrustes
 metrics = _sibling("train_utils")
+from mvp_benchmark_amd import pointwise as _pw, registration as _reg  # noqa: E402  (model_utils put the root on sys.path)
 
 EMB_DIMS, FF_DIMS, HEADS, STACK_DEPTH = 512, 1024, 4, 1
 
@@ -173,7 +176,33 @@ class DGCNN(nn.Module):
     def _stage(self, i, x):
         return F.relu(getattr(self, "bn%d" % i)(getattr(self, "conv%d" % i)(x)))
 
+    def _fused(self, x):
+        """Whether forward(x) takes the fused inference route (mvp_benchmark_amd.registration.edge_mlp_max, then conv5 as
+        one MFMA GEMM): the switch is on, BatchNorm uses its running statistics, x is on the op layer (float32 CUDA, at most
+        4 channels, rows of whole 16-byte groups) and nothing asks for a gradient -- the route has no backward."""
+        if not _reg.EDGE_MLP or self.training or not (x.is_cuda and x.dtype == torch.float32):
+            return False
+        if x.dim() != 3 or x.size(1) > 4 or x.size(2) % 4 != 0:
+            return False
+        return not (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())))
+
+    def _forward_fused(self, x):
+        """BatchNorm in eval mode is the per-channel map scale * t + shift; stages 1-4 and their maxima are one kernel, the
+        scale of stage 5 goes into conv5's weight and its shift is the GEMM's bias.  Nothing is kept between calls."""
+        bns = [getattr(self, "bn%d" % i) for i in range(1, 6)]
+        widths = [bn.num_features for bn in bns]
+        assert all(bn.eps == bns[0].eps for bn in bns)
+        scale = torch.cat([bn.weight for bn in bns]) / torch.sqrt(torch.cat([bn.running_var for bn in bns]) + bns[0].eps)
+        shift = torch.cat([bn.bias for bn in bns]) - torch.cat([bn.running_mean for bn in bns]) * scale
+        scales, shifts = scale.split(widths), shift.split(widths)
+        idx = _mu.knn(x, 20).transpose(1, 2)                          # (B, k, N)
+        pooled = _reg.edge_mlp_max(x, idx, [getattr(self, "conv%d" % i).weight for i in range(1, 5)], scales[:4], shifts[:4])
+        w5 = self.conv5.weight.view(widths[4], -1) * scales[4].unsqueeze(1)
+        return _pw.mfma_linear(pooled, w5.contiguous(), bias=shifts[4].contiguous(), relu=True)
+
     def forward(self, x):
+        if self._fused(x):
+            return self._forward_fused(x.detach())
         batch_size, _, num_points = x.size()
         # (B, 6, 20, N): knn + grouping operators; neighbours on the SLOW spatial axis (the stages are
         # 1x1 convolutions + per-channel BatchNorm: layout-agnostic; the reference keeps (B, 6, N, 20))

@@ -1,7 +1,8 @@
 """BASELINE cfg 5: DCP registration, 128 pairs of 1024 points, one MI355X -- forward (eval) and forward +
 backward (training step without the optimizer) timings, with the op-layer split from the torch profiler
-(kNN graph, neighbour gather / its gradient, the 3x3 Kabsch SVD launch).
-   python tools/bench_dcp.py            (MVP_BENCH_REPS: timed repetitions)"""
+(kNN graph, neighbour gather / its gradient, the 3x3 Kabsch SVD launch); then the same-process A/B of the fused edge MLP
+(mvp_benchmark_amd.registration.EDGE_MLP) on the eval forward, on emb_nn alone and on the edge stages alone.
+   python tools/bench_dcp.py            (MVP_BENCH_REPS: timed repetitions, MVP_BENCH_AB_ROUNDS: alternations, at least 5)"""
 import os, sys, time, types
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REG = os.path.join(ROOT, "registration")
@@ -73,3 +74,64 @@ for name, fn in (("forward", fwd), ("forward + backward", fwd_bwd)):
               name, total, knn, gather, scatter, svd, total - knn - gather - scatter - svd), flush=True)
     for r in sorted(rows, key=lambda r: -r[1])[:8]:
         print("      %-90s %8.3f ms x%d" % (r[0][:90], r[1], r[2]), flush=True)
+
+# ---- the fused edge MLP of DGCNN (mvp_benchmark_amd.registration.EDGE_MLP, default off): the two routes in this one process,
+# alternated (MVP_BENCH_AB_ROUNDS alternations, REPS repetitions each): the eval forward, emb_nn alone on both clouds, and
+# the edge stages alone (mvp_edge_mlp_max against the composed gather / conv / BatchNorm / ReLU / max chain).
+import mvp_benchmark_amd.registration as reg_ops
+ROUNDS = max(5, int(os.environ.get("MVP_BENCH_AB_ROUNDS", "5")))
+K_GRAPH, MAC_PER_COLUMN, PEAK = 20, 45440, 157.3         # 6*64 + 64*64 + 64*128 + 128*256 multiply-adds per edge; f32 MFMA TFLOP/s
+columns = 2 * B * N * K_GRAPH
+tflop = 2.0 * MAC_PER_COLUMN * columns / 1e12
+net.eval()
+clouds = (src.transpose(1, 2).contiguous(), tgt.transpose(1, 2).contiguous())
+emb = net.emb_nn
+
+
+def emb_both():
+    with torch.no_grad():
+        return [emb(c) for c in clouds]
+
+
+def edge_stages():
+    """Stages 1-4 and their maxima on both clouds, the graph given: the composed chain or the one kernel."""
+    with torch.no_grad():
+        for c, idx in zip(clouds, graphs):
+            if reg_ops.EDGE_MLP:
+                bns = [getattr(emb, "bn%d" % i) for i in range(1, 5)]
+                scales = [bn.weight / torch.sqrt(bn.running_var + bn.eps) for bn in bns]
+                shifts = [bn.bias - bn.running_mean * s for bn, s in zip(bns, scales)]
+                reg_ops.edge_mlp_max(c, idx, [getattr(emb, "conv%d" % i).weight for i in range(1, 5)], scales, shifts)
+            else:
+                nbr = dcp._mu.grouping_operation(c, idx)
+                edge = torch.cat((nbr, c.unsqueeze(2).expand(-1, -1, K_GRAPH, -1)), dim=1)
+                for i in range(1, 5):
+                    edge = emb._stage(i, edge)
+                    edge.max(dim=2, keepdim=True)
+
+
+with torch.no_grad():
+    graphs = [dcp._mu.knn(c, K_GRAPH).int().transpose(1, 2).contiguous() for c in clouds]
+print("# fused edge MLP A/B: %s; torch %s; %d alternations x %d repetitions, median ms [min .. max]; "
+      "edge stages = %d MAC x %.2f M columns = %.0f GFLOP, float32 MFMA peak %.1f TFLOP/s" % (
+          torch.cuda.get_device_name(0), torch.__version__, ROUNDS, REPS, MAC_PER_COLUMN, columns / 1e6, tflop * 1e3, PEAK),
+      flush=True)
+for name, fn in (("eval forward", fwd), ("emb_nn (kNN + edge stages + conv5), both clouds", emb_both),
+                 ("edge stages alone, both clouds", edge_stages)):
+    ms = {False: [], True: []}
+    for _ in range(ROUNDS):
+        for on in (False, True):
+            reg_ops.EDGE_MLP = on
+            try:
+                ms[on].append(timed(fn))
+            finally:
+                reg_ops.EDGE_MLP = False
+    med = {on: sorted(v)[len(v) // 2] for on, v in ms.items()}
+    print("  %-48s composed %7.2f [%7.2f .. %7.2f]   fused %7.2f [%7.2f .. %7.2f]   composed / fused %.2f" % (
+        name, med[False], min(ms[False]), max(ms[False]), med[True], min(ms[True]), max(ms[True]), med[False] / med[True]),
+        flush=True)
+    if fn is not fwd:
+        print("  %-48s composed %6.1f TFLOP/s (%4.1f %% of peak)   fused %6.1f TFLOP/s (%4.1f %% of peak)%s" % (
+            "  the edge stages' arithmetic over that time:", tflop / med[False] * 1e3, tflop / med[False] * 1e5 / PEAK,
+            tflop / med[True] * 1e3, tflop / med[True] * 1e5 / PEAK,
+            "" if fn is edge_stages else "   (kNN and conv5 inside the time)"), flush=True)
