@@ -660,7 +660,18 @@ int mvp_pointwise_max_backward(int b, int cin, int cout, int len, const float *x
  * H (b,3,3) row-major -> R (b,3,3) the rotation (reflection fix applied);
  * optional (may be NULL): U (b,3,3), S (b,3) descending, V (b,3,3) with
  * H = U diag(S) V^T (V WITHOUT the fix), flipped (b) = 1 where the fix applied.
- * One-sided Jacobi in float64 per matrix, outputs rounded to float32. */
+ * One-sided Jacobi in float64 per matrix, outputs rounded to float32.
+ * Domain.  R is defined, and accurate to an ulp of 1.0, wherever the two smallest singular values do not
+ * cancel behind the reflection (s_2 + d s_3 > 0, d = -1 where flipped): every H with det H > 0 down to rank 2,
+ * coinciding singular values included (U and V are then one valid choice among many; R does not depend on
+ * it), and every H with det H < 0 and s_3 < s_2.  At the poles of R (det H < 0 with s_2 = s_3, rank <= 1) the
+ * result is a finite proper rotation, one of the equally good ones; the zero matrix gives the identity.
+ * Every threshold is relative: scaling H by a power of two scales S and leaves R, U, V, flipped bit-equal.
+ * float32 subnormals are read as they are, not as zeros.  A matrix holding a NaN or an Inf gets R = NaN in
+ * all nine entries (never a plausible rotation) and the NaN / Inf in S; its U, V and flipped are unspecified;
+ * no other matrix of the batch is affected.
+ * The gradient of R with respect to H (registration.svd3_kabsch_backward, from U, S, V, flipped) is finite
+ * on the same domain: it divides by s_a + s_b, and by s_a - s_3 where flipped, never by s_a^2 - s_b^2. */
 int mvp_kabsch_svd3(int b, const float *H, float *R, float *U, float *S,
                     float *V, int *flipped, void *stream);
 

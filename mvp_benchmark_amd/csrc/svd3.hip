@@ -154,6 +154,15 @@ __global__ __launch_bounds__(64) void kabsch_svd3_kernel(int b, const float *__r
     V[2][2] = -V[2][2];
     make_r();
   }
+  // A NaN or an Inf in H: every inner product with its column is NaN or infinite, the rotation test above is false for
+  // it, the column stays as loaded and its norm is NaN / Inf.  The rank logic would then take that column for missing
+  // and complete U to a finite, plausible rotation: R is NaN instead (S carries the NaN / Inf as it is).
+  if (!(sg[0] + sg[1] + sg[2] < INFINITY)) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) Rm[r][c] = NAN;
+  }
 #pragma unroll
   for (int r = 0; r < 3; ++r)
 #pragma unroll

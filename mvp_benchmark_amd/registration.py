@@ -9,10 +9,17 @@
 
 B tiny LAPACK-style calls with a host synchronisation each become ONE launch of
 mvp_kabsch_svd3 (one lane per matrix, float64 one-sided Jacobi).  Differentiable:
-the backward pass is the closed-form SVD adjoint on (B,3,3) tensors (batched
+the backward pass is a closed-form adjoint on (B,3,3) tensors (batched
 elementwise / 3x3 matmul PyTorch ops, device-agnostic, no loop, no sync) -- the
-same gradient torch.svd's autograd produces for R = V D U^T with the reflection
-D held fixed.
+gradient torch.svd's autograd produces for R = V D U^T with the reflection D held
+fixed, in a form without that autograd's removable poles.
+
+Domain of the gradient: R is smooth, and svd3_kabsch_backward finite and accurate
+(32 * 2^-24 * max|grad_R| / min(s_i + e_ij s_j) in float32), wherever the two
+smallest singular values do not cancel: every H with det H > 0 down to rank 2,
+coinciding singular values included, and every H with det H < 0 whose s_3 stays
+below s_2.  s_2 = s_3 with det H < 0 and rank <= 1 are poles of R itself: that
+sample's gradient is inf / NaN, the rest of the batch is unaffected.
 
 The DeepGMR pieces (rri_features, gmm_params, gmm_register) follow at the end.
 """
@@ -28,28 +35,27 @@ def svd3_kabsch_backward(U, S, V, flipped, grad_R):
     """Adjoint of H -> R = V diag(1,1,d) U^T  (H = U diag(S) V^T, d = -1 where
     `flipped`) for batches of 3x3 matrices: returns grad_H (B,3,3).
 
-    dR = dV D U^T + V D dU^T  =>  gU = gR^T V D,  gV = gR U D,  gS = 0, then the
-    SVD adjoint for square full-rank A (Townsend 2016; the formula behind
-    torch.linalg.svd's autograd):
-        gA = U [ (skew(U^T gU) / E) S + S (skew(V^T gV) / E) ] V^T,
-        skew(X) = X - X^T,  E_ij = s_j^2 - s_i^2 (i != j), E_ii = 1.
-    Singular where two singular values coincide, exactly like torch.svd."""
+    With dU = U Wu, dV = V Wv (Wu, Wv skew):
+        P = U^T dH V = Wu S - S Wv + dS,      W = V^T dR U = Wv D - D Wu.
+    For a != b the pair (P_ab, P_ba) determines (Wu_ab, Wv_ab) through a 2x2 system of determinant s_b^2 - s_a^2;
+    in W_ab = d_b Wv_ab - d_a Wu_ab one factor of that determinant cancels (e_ab = d_a d_b):
+        W_ab = d_b (P_ba / (s_b + e_ab s_a) - P_ab / (s_a + e_ab s_b)),      W_aa = 0,
+    so with Q = V^T gR U and <gR, dR> = <Q, W> = <G, P>:
+        G_ab = (d_a Q_ba - d_b Q_ab) / (s_a + e_ab s_b)   (a != b),   G_aa = 0,      gH = U G V^T.
+    The denominators are s_a + s_b between unflipped directions and s_a - s_3 against a flipped third one: the
+    formula is singular exactly where R is -- s_2 = s_3 (or s_1 = s_3) with det H < 0, and rank <= 1 -- and nowhere
+    else; s_1 = s_2, and s_2 = s_3 with det H > 0, are ordinary points (the general SVD adjoint, which divides by
+    s_b^2 - s_a^2, has removable poles there: NaN at an exact coincidence, float32 noise of 6e-8 / gap near one).
+    At a true pole the sample's own gradient is inf or NaN (IEEE division, nothing masked); no other sample of the
+    batch is touched.  float32 error on clustered spectra: tests/test_kabsch_cpu.py."""
     d = torch.ones_like(S)
     d[:, 2] = torch.where(flipped.bool(), -torch.ones_like(S[:, 2]), torch.ones_like(S[:, 2]))
-    VD = V * d.unsqueeze(1)                       # V diag(d)
-    UD = U * d.unsqueeze(1)
-    gU = grad_R.transpose(1, 2) @ VD
-    gV = grad_R @ UD
-    s2 = S * S
-    E = s2.unsqueeze(1) - s2.unsqueeze(2)         # E_ij = s_j^2 - s_i^2
-    eye = torch.eye(3, dtype=S.dtype, device=S.device)
-    E = E + eye
-    Su = U.transpose(1, 2) @ gU
-    Sv = V.transpose(1, 2) @ gV
-    Ju = (Su - Su.transpose(1, 2)) / E * (1 - eye)
-    Jv = (Sv - Sv.transpose(1, 2)) / E * (1 - eye)
-    inner = Ju * S.unsqueeze(1) + S.unsqueeze(2) * Jv
-    return U @ inner @ V.transpose(1, 2)
+    Q = V.transpose(1, 2) @ grad_R @ U
+    off = 1 - torch.eye(3, dtype=S.dtype, device=S.device)
+    den = S.unsqueeze(2) + (d.unsqueeze(2) * d.unsqueeze(1)) * S.unsqueeze(1)     # s_a + e_ab s_b
+    num = d.unsqueeze(2) * Q.transpose(1, 2) - d.unsqueeze(1) * Q
+    G = torch.where(off.bool(), num / den, torch.zeros_like(num))                 # G_aa = 0 (0 / 0 at s_a = 0)
+    return U @ G @ V.transpose(1, 2)
 
 
 class KabschSVD(Function):
@@ -224,7 +230,10 @@ def gmm_params(logits, xyz):
 
 
 def _kabsch_reference(H):
-    """R = V diag(1, 1, det(V U^T)) U^T of H = U S V^T in torch (gmm_register's torch.svd + determinant)."""
+    """R = V diag(1, 1, det(V U^T)) U^T of H = U S V^T in torch (gmm_register's torch.svd + determinant).  Its gradient
+    is the reference's: torch.linalg.svd's autograd, which divides by s_j^2 - s_i^2 and is singular at EVERY coincidence
+    of two singular values (NaN at an exact one, error ~ eps / gap near one), where the device path's adjoint
+    (svd3_kabsch_backward) is not.  No reference for a gradient near a cluster."""
     U, _, Vh = torch.linalg.svd(H)
     V = Vh.transpose(1, 2)
     d = torch.ones(H.shape[0], 3, dtype=H.dtype, device=H.device)

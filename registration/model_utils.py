@@ -67,7 +67,11 @@ def get_graph_feature(x, k=20, k_major=False):
 def procrustes(src, src_corr, weights=None):
     """Rigid motion taking src (B,3,N) onto src_corr (B,3,N): the SVD head
     (dcp.py:345-376; with `weights` (B,1,N): model_utils.py:221-255).
-    Returns R (B,3,3), t (B,3)."""
+    Returns R (B,3,3), t (B,3).
+    float32 CUDA tensors: kabsch_rotation, whose gradient is finite wherever R is smooth (coinciding singular values
+    of H included: a cloud with a symmetry axis).  Other tensors: the reference's torch.linalg.svd, whose autograd
+    divides by s_j^2 - s_i^2 and is singular at every coincidence of two singular values, where the device path's is
+    not; no reference for a gradient near a cluster."""
     src_mean = src.mean(dim=2, keepdim=True)
     corr_mean = src_corr.mean(dim=2, keepdim=True)
     src_centered = src - src_mean

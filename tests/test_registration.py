@@ -179,6 +179,11 @@ def test_kabsch_svd3_degenerate_inputs():
 
 @pytest.mark.gpu
 def test_kabsch_rotation_gradient():
+    """64 randn matrices, none left out: every gradient within 32 * 2^-24 * max|g| / conditioning(H) of float64
+    autograd (tests/kabsch_cases.py derives the bound; observed on an MI355X: 0.18 of it).  The reference differentiates
+    through torch.linalg.svd, which is sound here and only here: the smallest relative gap of these 64 spectra is
+    asserted to be above 1e-3, where float64 loses six of its sixteen digits.  Clustered spectra: test_gpu_kabsch.py."""
+    import kabsch_cases
     from mvp_benchmark_amd.registration import kabsch_rotation
     torch.manual_seed(3)
     H = torch.randn(64, 3, 3)
@@ -193,10 +198,13 @@ def test_kabsch_rotation_gradient():
     d[:, 2] = torch.where(torch.linalg.det(V @ U.transpose(1, 2)) < 0, -1.0, 1.0)
     R64 = (V * d.unsqueeze(1)) @ U.transpose(1, 2)
     want, = torch.autograd.grad((R64 * g.double()).sum(), H64)
-    well = (S[:, 0] - S[:, 1] > 0.05) & (S[:, 1] - S[:, 2] > 0.05)          # away from the adjoint's poles
-    assert int(well.sum()) > 40
+    Sd = S.detach()
+    assert float(torch.minimum(Sd[:, 0] - Sd[:, 1], Sd[:, 1] - Sd[:, 2]).div(Sd[:, 0]).min()) > 1e-3   # the REFERENCE's poles
     np.testing.assert_allclose(R.detach().cpu().numpy(), R64.detach().float().numpy(), atol=2e-6)
-    np.testing.assert_allclose(Hd.grad.cpu().numpy()[well.numpy()], want.float().numpy()[well.numpy()], rtol=2e-3, atol=2e-3)
+    bound = kabsch_cases.gradient_bound(H.numpy(), g.numpy())
+    err = (Hd.grad.cpu().double() - want).abs().amax(dim=(1, 2)).numpy()
+    print("kabsch_rotation gradient, 64 randn matrices: max error / bound = %.3g" % (err / bound).max())
+    assert np.isfinite(err).all() and (err <= bound).all(), (err / bound).max()
 
 
 @pytest.mark.gpu
