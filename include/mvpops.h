@@ -43,7 +43,7 @@ extern "C" {
 #define MVP_ELAUNCH (-3)
 
 /* ABI version of this header; bumped on any signature change. */
-#define MVP_ABI_VERSION 22
+#define MVP_ABI_VERSION 23
 int mvp_abi_version(void);
 
 /* hipGetErrorString of the last launch failure seen on the calling thread
@@ -674,6 +674,42 @@ int mvp_pointwise_max_backward(int b, int cin, int cout, int len, const float *x
  * on the same domain: it divides by s_a + s_b, and by s_a - s_3 where flipped, never by s_a^2 - s_b^2. */
 int mvp_kabsch_svd3(int b, const float *H, float *R, float *U, float *S,
                     float *V, int *flipped, void *stream);
+
+/* ------------------------------------- registration (DCP) transformer */
+
+/* ABI 23.  The transformer's own normalisation (registration/models/dcp.py:139-149: `a_2 * (x - mean) / (std + eps) +
+ * b_2`, std unbiased, eps added to the std -- not nn.LayerNorm) with the residual sum in front of it, one read and one
+ * write of a row (two writes with the sum) where the reference runs two reductions, four elementwise passes and an
+ * addition of its own.
+ * x (rows,d); delta (rows,d) or NULL; a, b (d); sum (rows,d) or NULL, receives z = x + delta (one float add; z = x when
+ * delta is NULL) and is required when delta is given; y (rows,d); stats (rows,2) or NULL, receives {mean, std} per row.
+ * Per row:  mean = sum(z) / d (a true division),  c = z - mean,  std = sqrt(sum(c * c) / (d - 1)) from the CENTRED
+ * values (never E[z^2] - mean^2),  y = (a * c) * (1 / (std + eps)) + b.
+ * d % 4 == 0 and 4 <= d <= 1024, rows * d < 2^31 (else MVP_EBADSHAPE); eps >= 0 and finite, x / delta / sum / y 16-byte
+ * aligned (else MVP_EBADARG); these refusals are decided before the null checks.  rows == 0 does nothing.
+ * A constant row has std = 0 and y = b exactly (eps > 0).  A row that holds a NaN or an Inf gets y = NaN in all its d
+ * entries (and NaN statistics); no other row changes.  One wave per row, fixed summation order: the same bits on every
+ * run, on every device. */
+int mvp_ref_layernorm(int rows, int d, const float *x, const float *delta, const float *a, const float *b, float eps,
+                      float *sum, float *y, float *stats, void *stream);
+
+/* Its backward pass, from z and the row statistics alone.  z (rows,d) = what was normalised (the forward's sum, or x);
+ * gy (rows,d) the gradient of y; gres (rows,d) or NULL the gradient that reaches z directly, through the residual
+ * stream; stats as written by the forward pass, eps the forward's.  With U = 1 / (std + eps), gh = gy * a:
+ *   gz_i = U * (gh_i - mean(gh)) - c_i * (sum_j gh_j c_j) * U^2 / ((d - 1) * std)   [+ gres_i, the last single float add]
+ *   ga[j] = sum_r gy[r,j] * c[r,j] * U_r,    gb[j] = sum_r gy[r,j]
+ * The second term of gz is taken as 0 where std == 0 (what torch's std backward does: it masks a zero std).
+ * c = z - mean is re-centred on the row's mean taken to double (stats' float32 mean is its first approximation), so a
+ * centred value near the mean keeps its digits: ga over few rows depends on them.
+ * gz, ga, gb are overwritten (rows == 0 writes nothing).  ga and gb may each be NULL; with both NULL no scratch is needed,
+ * otherwise `scratch` holds mvp_ref_layernorm_backward_scratch_bytes(rows, d) bytes (16-byte aligned; one slab [2][d]
+ * per workgroup, added in a fixed order by a second small launch: no atomics, bit-reproducible).  Shapes, alignment
+ * (z, gy, gres, gz) and the order of the refusals as in the forward pass.  A non-finite row (NaN statistics) gets
+ * gz = NaN in all its entries; a column of ga / gb is NaN if a contributing row is. */
+long long mvp_ref_layernorm_backward_scratch_bytes(int rows, int d);
+int mvp_ref_layernorm_backward(int rows, int d, const float *z, const float *a, const float *gy, const float *gres,
+                               const float *stats, float eps, float *gz, float *ga, float *gb, void *scratch,
+                               long long scratch_bytes, void *stream);
 
 /* ------------------------------------------- registration (DeepGMR) head */
 

@@ -65,11 +65,13 @@ SIGNATURES = {
     "mvp_rri_features": "iiippp",
     "mvp_gmm_params": "iiipppppp",
     "mvp_gmm_params_backward": "iiippppppppp",
+    "mvp_ref_layernorm": "iippppfppp",
+    "mvp_ref_layernorm_backward": "iipppppfppppq",
 }
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "f": ctypes.c_float,
        "q": ctypes.c_longlong}
 
-ABI_VERSION = 22  # MVP_ABI_VERSION of include/mvpops.h this binding was written against
+ABI_VERSION = 23  # MVP_ABI_VERSION of include/mvpops.h this binding was written against
 
 # default of mvp_emd_configure's `split` knob (csrc/emd.hip: emd_knobs)
 EMD_DEFAULT_SPLIT = 5
@@ -123,6 +125,8 @@ def load():
     lib.mvp_share_gather_sum_lds_bytes.argtypes = [ctypes.c_int] * 2
     lib.mvp_dense_edge_conv_scratch_bytes.restype = ctypes.c_longlong
     lib.mvp_dense_edge_conv_scratch_bytes.argtypes = [ctypes.c_int] * 5
+    lib.mvp_ref_layernorm_backward_scratch_bytes.restype = ctypes.c_longlong
+    lib.mvp_ref_layernorm_backward_scratch_bytes.argtypes = [ctypes.c_int] * 2
     for name, sig in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype = ctypes.c_int
@@ -283,11 +287,16 @@ def dense_edge_conv_scratch_bytes(b, g, layers, k, n):
     return int(load().mvp_dense_edge_conv_scratch_bytes(int(b), int(g), int(layers), int(k), int(n)))
 
 
+def ref_layernorm_backward_scratch_bytes(rows, d):
+    """Scratch of mvp_ref_layernorm_backward's ga / gb (0: shape refused or no rows).  No GPU needed."""
+    return int(load().mvp_ref_layernorm_backward_scratch_bytes(int(rows), int(d)))
+
+
 def exported_symbols():
     """All entry points include/mvpops.h declares."""
     return ["mvp_abi_version", "mvp_last_hip_error", "mvp_emd_scratch_bytes", "mvp_emd_configure", "mvp_chamfer_scratch_bytes", "mvp_knn_scratch_bytes", "mvp_fps_scratch_bytes", "mvp_fps_cluster_scratch_bytes",
             "mvp_scatter_scratch_bytes", "mvp_pointwise_wgrad_scratch_bytes", "mvp_pointwise_wgrad_mfma_scratch_bytes",
             "mvp_pointwise_mfma_splitk_plan", "mvp_pointwise_mfma_splitk_scratch_bytes",
             "mvp_pointwise_max_backward_scratch_bytes", "mvp_share_gather_sum_lds_bytes",
-            "mvp_dense_edge_conv_scratch_bytes"] \
+            "mvp_dense_edge_conv_scratch_bytes", "mvp_ref_layernorm_backward_scratch_bytes"] \
         + list(SIGNATURES)

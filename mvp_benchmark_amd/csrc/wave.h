@@ -41,6 +41,41 @@ __device__ __forceinline__ T wave_max(T v) {
   return read_lane(dpp_max<0x143, 0xC>(half32_max(v)), 63);  // row_bcast31 -> rows 2, 3
 }
 
+// v + (v as permuted by the DPP control CTRL): ONE DPP-fused v_add per step (a double's two halves travel separately); a
+// lane a row mask leaves unwritten adds 0.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ float dpp_add(float v) {
+  return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xF, false));
+}
+__device__ __forceinline__ double double_of(unsigned lo, unsigned hi) {
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double dpp_add(double v) {
+  const long long b = __double_as_longlong(v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)b, CTRL, ROW_MASK, 0xF, false);
+  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, ROW_MASK, 0xF, false);
+  return v + double_of(lo, hi);
+}
+__device__ __forceinline__ double read_lane(double v, int l) {
+  const long long b = __double_as_longlong(v);
+  return double_of(read_lane((unsigned)b, l), read_lane((unsigned)(b >> 32), l));
+}
+// wave_sum: the sum of all 64 lanes (float or double), wave-uniform (taken from lane 63), in the six steps of wave_max: a
+// butterfly inside the rows of 16 (both operands of every step are the same pair of partial sums, so the lanes of a row
+// agree bit for bit), then row 0 into row 1 and row 2 into row 3, then the lower half into the upper.  A fixed tree: the
+// same bits on every run; a NaN or an Inf in any lane reaches the result.
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+  v = dpp_add<0xB1, 0xF>(v);   // quad_perm [1,0,3,2]
+  v = dpp_add<0x4E, 0xF>(v);   // quad_perm [2,3,0,1]
+  v = dpp_add<0x141, 0xF>(v);  // row_half_mirror
+  v = dpp_add<0x140, 0xF>(v);  // row_mirror
+  v = dpp_add<0x142, 0xA>(v);  // row_bcast15 -> rows 1, 3
+  v = dpp_add<0x143, 0xC>(v);  // row_bcast31 -> rows 2, 3
+  return read_lane(v, 63);
+}
+
 // Axis-aligned box of the wave's 64 per-lane boxes, in every lane.
 __device__ __forceinline__ void wave_box(float (&lo)[3], float (&hi)[3]) {
 #pragma unroll

@@ -21,14 +21,15 @@ coinciding singular values included, and every H with det H < 0 whose s_3 stays
 below s_2.  s_2 = s_3 with det H < 0 and rank <= 1 are poles of R itself: that
 sample's gradient is inf / NaN, the rest of the batch is unaffected.
 
-The DeepGMR pieces (rri_features, gmm_params, gmm_register) follow at the end.
+The DeepGMR pieces (rri_features, gmm_params, gmm_register) follow, then DCP's fused edge MLP (edge_mlp_max) and the
+transformer's LayerNorm with its residual sum (ref_layer_norm).
 """
 import math
 
 import torch
 from torch.autograd import Function
 
-from ._lib import call
+from ._lib import call, ref_layernorm_backward_scratch_bytes
 
 
 def svd3_kabsch_backward(U, S, V, flipped, grad_R):
@@ -307,3 +308,112 @@ def edge_mlp_max(x, idx, weights, scales, shifts):
     call("mvp_edge_mlp_max", x.device, B, c, N, k, len(weights), *widths, x.detach().contiguous(),
          idx.int().contiguous(), w, scale, shift, out)
     return out
+
+
+# ------------------------------------------------------------------------ the transformer's LayerNorm + residual sums (DCP)
+# registration/models/dcp.py: LayerNorm -- a_2 * (x - mean) / (std + eps) + b_2 with the unbiased std and eps added to the
+# std -- and the residual addition in front of it, as one kernel each way (mvp_ref_layernorm[_backward],
+# csrc/layer_norm.hip).
+
+LAYER_NORM = False         # True: LayerNorm.forward and the transformer's residual sums take ref_layer_norm
+
+
+def _layer_norm_reference(z, a, b, eps):
+    """The module's own formula, op for op (registration/models/dcp.py: LayerNorm.forward)."""
+    centred = z - z.mean(-1, keepdim=True)
+    return a * centred / (z.std(-1, keepdim=True) + eps) + b
+
+
+def ref_layer_norm_backward_reference(z, a, gy, eps, gres=None):
+    """The closed form mvp_ref_layernorm_backward computes, in torch: z (..., d) what was normalised, gy the gradient of y,
+    gres the gradient reaching z directly -> (gz, ga, gb).  U = 1 / (std + eps), gh = gy * a:
+        gz = U (gh - mean gh) - c (sum gh c) U^2 / ((d - 1) std)  [+ gres],   ga = sum_r gy c U,   gb = sum_r gy,
+    the second term 0 where std == 0 (torch's std backward masks a zero std)."""
+    d = z.shape[-1]
+    c = z - z.mean(-1, keepdim=True)
+    std = torch.sqrt((c * c).sum(-1, keepdim=True) / (d - 1))
+    U = 1 / (std + eps)
+    gh = gy * a
+    coef = torch.where(std == 0, torch.zeros_like(std), (gh * c).sum(-1, keepdim=True) * U * U / ((d - 1) * std))
+    gz = U * (gh - gh.mean(-1, keepdim=True)) - c * coef
+    if gres is not None:
+        gz = gz + gres
+    return gz, (gy * c * U).reshape(-1, d).sum(0), gy.reshape(-1, d).sum(0)
+
+
+def _layer_norm_fits(x, a, b, residual):
+    """Whether mvp_ref_layernorm takes these tensors as they are: float32 CUDA, contiguous, rows on 16-byte addresses, a row
+    length the kernel covers."""
+    d = x.shape[-1] if x.dim() >= 1 else 0
+    if not (d % 4 == 0 and 4 <= d <= 1024 and x.numel() < 2 ** 31 and a.shape == b.shape == (d,)):
+        return False
+    tensors = (x, a, b) if residual is None else (x, a, b, residual)
+    if not all(_on_op_layer(t) and t.is_contiguous() and t.device == x.device for t in tensors):
+        return False
+    if x.data_ptr() % 16 != 0 or (residual is not None and residual.data_ptr() % 16 != 0):
+        return False
+    return residual is None or residual.shape == x.shape
+
+
+def _aligned_rows(g):
+    """A gradient as the kernel reads it: float32, contiguous, on a 16-byte address (autograd may hand over a view)."""
+    g = g.float().contiguous()
+    return g if g.data_ptr() % 16 == 0 else g.clone()
+
+
+class RefLayerNorm(Function):
+    """(x (..., d), a (d), b (d), eps, residual (..., d) or None) -> y, or (x + residual, y): mvp_ref_layernorm, float32
+    CUDA only (ref_layer_norm decides).  Saves z (the sum, or x), a and the (rows, 2) row statistics, nothing else."""
+
+    @staticmethod
+    def forward(ctx, x, a, b, eps, residual):
+        d = x.shape[-1]
+        rows = x.numel() // d
+        y = torch.empty_like(x)
+        total = torch.empty_like(x) if residual is not None else None
+        wants = any(ctx.needs_input_grad)
+        stats = torch.empty(rows, 2, device=x.device, dtype=torch.float32) if wants else None
+        call("mvp_ref_layernorm", x.device, rows, d, x, residual, a, b, eps, total, y, stats)
+        ctx.eps, ctx.with_residual = eps, residual is not None
+        ctx.set_materialize_grads(False)
+        if wants:
+            ctx.save_for_backward(x if total is None else total, a, stats)
+        return y if total is None else (total, y)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        z, a, stats = ctx.saved_tensors
+        gres, gy = grads if ctx.with_residual else (None, grads[0])
+        need_x = ctx.needs_input_grad[0] or ctx.needs_input_grad[4]
+        need_a, need_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        d = z.shape[-1]
+        rows = z.numel() // d
+        if gy is None:                                          # y was not used: only the residual stream passes through
+            gz, ga, gb = gres, (torch.zeros_like(a) if need_a else None), (torch.zeros_like(a) if need_b else None)
+        else:
+            gy, gres = _aligned_rows(gy), (None if gres is None else _aligned_rows(gres))
+            gz = torch.empty_like(z)
+            ga = torch.empty_like(a) if need_a else None
+            gb = torch.empty_like(a) if need_b else None
+            nbytes = ref_layernorm_backward_scratch_bytes(rows, d) if need_a or need_b else 0
+            scratch = torch.empty(nbytes, device=z.device, dtype=torch.uint8) if nbytes else None
+            if rows == 0:                                       # nothing is launched, nothing written
+                ga, gb = (None if ga is None else ga.zero_()), (None if gb is None else gb.zero_())
+            call("mvp_ref_layernorm_backward", z.device, rows, d, z, a, gy, gres, stats, ctx.eps, gz, ga, gb, scratch, nbytes)
+        if not need_x:
+            gz = None
+        return (gz if ctx.needs_input_grad[0] else None, ga, gb, None, gz if ctx.needs_input_grad[4] else None)
+
+
+def ref_layer_norm(x, a, b, eps=1e-6, residual=None):
+    """The transformer's normalisation of z = x (+ residual) over the last axis: a * (z - mean) / (std + eps) + b, std
+    unbiased.  Returns y, or (x + residual, y) when a residual is given -- the sum is the residual stream's next value, so
+    `x = x + f(...); h = norm(x)` is one call.  float32 CUDA contiguous tensors with d % 4 == 0, 4 <= d <= 1024 run
+    mvp_ref_layernorm (backward: mvp_ref_layernorm_backward; gradients for x, a, b and the residual, whose gradient equals
+    x's); CPU tensors, float64, any other d and non-contiguous input take the module's formula composed in torch."""
+    if _layer_norm_fits(x, a, b, residual):
+        return RefLayerNorm.apply(x, a, b, float(eps), residual)
+    if residual is None:
+        return _layer_norm_reference(x, a, b, eps)
+    z = x + residual
+    return z, _layer_norm_reference(z, a, b, eps)

@@ -12,7 +12,8 @@ advanced indexing) and the SVD head (one mvp_kabsch_svd3 launch instead of B
 torch.svd / torch.det calls with a host synchronisation each).  Attention and
 the 1x1 convolutions are library GEMMs -- except on DGCNN's opt-in inference route
 (mvp_benchmark_amd.registration.EDGE_MLP), which runs the four edge stages and their
-maxima as one kernel and conv5 as one MFMA GEMM.
+maxima as one kernel and conv5 as one MFMA GEMM.  The transformer's LayerNorm and residual sums have an opt-in route of
+their own (mvp_benchmark_amd.registration.LAYER_NORM): every `x + f(...)` followed by a norm is one kernel, each way.
 """
 import copy
 import math
@@ -60,7 +61,11 @@ class LayerNorm(nn.Module):
         self.b_2 = nn.Parameter(torch.zeros(features))
         self.eps = eps
 
-    def forward(self, x):
+    def forward(self, x, residual=None):
+        """norm(x); with a residual (only on the fused route): (x + residual, norm(x + residual)), one kernel."""
+        if _reg.LAYER_NORM:
+            return _reg.ref_layer_norm(x, self.a_2, self.b_2, self.eps, residual)
+        assert residual is None
         centred = x - x.mean(-1, keepdim=True)
         return self.a_2 * centred / (x.std(-1, keepdim=True) + self.eps) + self.b_2
 
@@ -121,6 +126,9 @@ class TransformerLayer(nn.Module):
         self.sublayer = nn.ModuleList([SublayerConnection(size) for _ in range(2 if src_attn is None else 3)])
 
     def forward(self, x, memory=None):
+        if _reg.LAYER_NORM:
+            x, last = self.forward_deferred(x, memory)
+            return x + last
         h = self.sublayer[0].norm(x)
         x = x + self.self_attn(h, h)
         branch = 1
@@ -128,6 +136,21 @@ class TransformerLayer(nn.Module):
             x = x + self.src_attn(self.sublayer[1].norm(x), memory)
             branch = 2
         return x + self.feed_forward(self.sublayer[branch].norm(x))
+
+    def forward_deferred(self, x, memory=None, pending=None):
+        """The fused route (mvp_benchmark_amd.registration.LAYER_NORM): every branch's output is the `residual` of the NEXT
+        norm, which adds it to the stream and normalises the sum in one kernel.  `pending`: the previous layer's last branch,
+        not yet added to x.  -> (x, last): the layer's output is x + last, left to whoever normalises it next."""
+        norm = lambda i, x, branch: (x, self.sublayer[i].norm(x)) if branch is None else self.sublayer[i].norm(x, branch)
+        x, h = norm(0, x, pending)
+        branch = self.self_attn(h, h)
+        i = 1
+        if memory is not None:
+            x, h = norm(1, x, branch)
+            branch = self.src_attn(h, memory)
+            i = 2
+        x, h = norm(i, x, branch)
+        return x, self.feed_forward(h)
 
 
 class LayerStack(nn.Module):
@@ -137,6 +160,11 @@ class LayerStack(nn.Module):
         self.norm = LayerNorm(layer.size)
 
     def forward(self, x, memory=None):
+        if _reg.LAYER_NORM:
+            pending = None                # a layer's last sum joins the next layer's first norm, or the final one
+            for layer in self.layers:
+                x, pending = layer.forward_deferred(x, memory, pending)
+            return self.norm(x) if pending is None else self.norm(x, pending)[1]
         for layer in self.layers:
             x = layer(x, memory)
         return self.norm(x)

@@ -1,7 +1,9 @@
 """BASELINE cfg 5: DCP registration, 128 pairs of 1024 points, one MI355X -- forward (eval) and forward +
 backward (training step without the optimizer) timings, with the op-layer split from the torch profiler
 (kNN graph, neighbour gather / its gradient, the 3x3 Kabsch SVD launch); then the same-process A/B of the fused edge MLP
-(mvp_benchmark_amd.registration.EDGE_MLP) on the eval forward, on emb_nn alone and on the edge stages alone.
+(mvp_benchmark_amd.registration.EDGE_MLP) on the eval forward, on emb_nn alone and on the edge stages alone; then the same for
+the transformer's fused LayerNorm + residual sums (mvp_benchmark_amd.registration.LAYER_NORM): eval forward, forward + backward,
+the transformer alone, the training step's peak memory per route, and the two kernels alone with their bytes/s.
    python tools/bench_dcp.py            (MVP_BENCH_REPS: timed repetitions, MVP_BENCH_AB_ROUNDS: alternations, at least 5)"""
 import os, sys, time, types
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -135,3 +137,88 @@ for name, fn in (("eval forward", fwd), ("emb_nn (kNN + edge stages + conv5), bo
             "  the edge stages' arithmetic over that time:", tflop / med[False] * 1e3, tflop / med[False] * 1e5 / PEAK,
             tflop / med[True] * 1e3, tflop / med[True] * 1e5 / PEAK,
             "" if fn is edge_stages else "   (kNN and conv5 inside the time)"), flush=True)
+
+# ---- the transformer's LayerNorm + residual sums as kernels (mvp_benchmark_amd.registration.LAYER_NORM, default off): the two
+# routes in this one process, alternated like the block above: the eval forward, the training step (forward + backward), the
+# transformer alone both ways; the training step's peak memory per route; then the two kernels alone at cfg 5's row count.
+from mvp_benchmark_amd import _lib
+
+
+def pointer_eval():
+    with torch.no_grad():
+        return net.pointer(f_src, f_tgt)
+
+
+def pointer_train():
+    net.pointer.zero_grad(set_to_none=True)
+    p_src, p_tgt = net.pointer(f_src, f_tgt)
+    (p_src.sum() + p_tgt.sum()).backward()
+
+
+net.eval()
+with torch.no_grad():
+    f_src, f_tgt = net.emb_nn(clouds[0]), net.emb_nn(clouds[1])
+print("# fused LayerNorm + residual A/B: %d alternations x %d repetitions, median ms [min .. max]; 14 norms and 10 residual "
+      "sums per forward over (%d, %d) rows" % (ROUNDS, REPS, B * N, dcp.EMB_DIMS), flush=True)
+faster = {}
+for name, fn, training in (("eval forward", fwd, False), ("forward + backward", fwd_bwd, True),
+                           ("transformer alone, eval forward", pointer_eval, False),
+                           ("transformer alone, forward + backward", pointer_train, True)):
+    (net.train() if training else net.eval())
+    ms = {False: [], True: []}
+    for _ in range(ROUNDS):
+        for on in (False, True):
+            reg_ops.LAYER_NORM = on
+            try:
+                ms[on].append(timed(fn))
+            finally:
+                reg_ops.LAYER_NORM = False
+    med = {on: sorted(v)[len(v) // 2] for on, v in ms.items()}
+    faster[name] = all(f < c for f, c in zip(ms[True], ms[False]))
+    print("  %-40s composed %7.2f [%7.2f .. %7.2f]   fused %7.2f [%7.2f .. %7.2f]   composed / fused %.3f   fused faster in "
+          "every alternation: %s" % (name, med[False], min(ms[False]), max(ms[False]), med[True], min(ms[True]),
+                                     max(ms[True]), med[False] / med[True], "yes" if faster[name] else "NO"), flush=True)
+print("  criterion (fused faster than composed in every alternation, eval forward and forward + backward): %s" % (
+    "met" if faster["eval forward"] and faster["forward + backward"] else "NOT met -- the switch stays off either way"), flush=True)
+net.train()
+for on in (False, True):
+    reg_ops.LAYER_NORM = on
+    try:
+        fwd_bwd(); torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        fwd_bwd(); torch.cuda.synchronize()
+        print("  training step, %s route: torch.cuda.max_memory_allocated %.2f GB" % (
+            "fused" if on else "composed", torch.cuda.max_memory_allocated() / 1e9), flush=True)
+    finally:
+        reg_ops.LAYER_NORM = False
+net.zero_grad(set_to_none=True)
+
+ROWS_LN, D_LN, HBM_SPEC, HBM_COPY = B * N, dcp.EMB_DIMS, 8.0, 6.29       # TB/s: MI355X spec, measured float4 copy
+gl = torch.Generator().manual_seed(6)
+xs, ds_, gys, grs = ((torch.randn(ROWS_LN, D_LN, generator=gl) + 0.5).to(dev) for _ in range(4))
+al, bl = torch.randn(D_LN, generator=gl).to(dev), torch.randn(D_LN, generator=gl).to(dev)
+zs, ys, gzs = torch.empty_like(xs), torch.empty_like(xs), torch.empty_like(xs)
+st = torch.empty(ROWS_LN, 2, device=dev)
+gal, gbl = torch.empty_like(al), torch.empty_like(al)
+nb = _lib.ref_layernorm_backward_scratch_bytes(ROWS_LN, D_LN)
+scr = torch.empty(nb, device=dev, dtype=torch.uint8)
+tensor_bytes = ROWS_LN * D_LN * 4
+kernels = (
+    ("mvp_ref_layernorm, residual (2 reads + 2 writes)", 4,
+     lambda: _lib.call("mvp_ref_layernorm", dev, ROWS_LN, D_LN, xs, ds_, al, bl, 1e-6, zs, ys, st)),
+    ("mvp_ref_layernorm, no residual (1 read + 1 write)", 2,
+     lambda: _lib.call("mvp_ref_layernorm", dev, ROWS_LN, D_LN, xs, None, al, bl, 1e-6, None, ys, st)),
+    ("mvp_ref_layernorm_backward, gres, ga / gb (3 reads + 1 write)", 4,
+     lambda: _lib.call("mvp_ref_layernorm_backward", dev, ROWS_LN, D_LN, zs, al, gys, grs, st, 1e-6, gzs, gal, gbl, scr, nb)),
+    ("mvp_ref_layernorm_backward, no gres, ga / gb (2 reads + 1 write)", 3,
+     lambda: _lib.call("mvp_ref_layernorm_backward", dev, ROWS_LN, D_LN, zs, al, gys, None, st, 1e-6, gzs, gal, gbl, scr, nb)),
+    ("mvp_ref_layernorm_backward, no gres, no ga / gb (2 reads + 1 write)", 3,
+     lambda: _lib.call("mvp_ref_layernorm_backward", dev, ROWS_LN, D_LN, zs, al, gys, None, st, 1e-6, gzs, None, None, None, 0)),
+)
+print("# the kernels alone at (%d, %d) float32, %.0f MB a tensor; bytes/s from the algorithmic bytes; HBM %.1f TB/s spec, "
+      "%.2f TB/s measured float4 copy" % (ROWS_LN, D_LN, tensor_bytes / 1e6, HBM_SPEC, HBM_COPY), flush=True)
+for name, passes, fn in kernels:
+    t = sorted(timed(fn, 20) for _ in range(5))[2]
+    rate = passes * tensor_bytes / t / 1e9                                  # TB/s: bytes / ms / 1e9
+    print("  %-70s %7.3f ms  %5.2f TB/s = %4.1f %% of spec, %4.1f %% of the copy rate" % (
+        name, t, rate, rate / HBM_SPEC * 100, rate / HBM_COPY * 100), flush=True)
