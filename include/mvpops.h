@@ -43,7 +43,7 @@ extern "C" {
 #define MVP_ELAUNCH (-3)
 
 /* ABI version of this header; bumped on any signature change. */
-#define MVP_ABI_VERSION 23
+#define MVP_ABI_VERSION 24
 int mvp_abi_version(void);
 
 /* hipGetErrorString of the last launch failure seen on the calling thread
@@ -710,6 +710,57 @@ long long mvp_ref_layernorm_backward_scratch_bytes(int rows, int d);
 int mvp_ref_layernorm_backward(int rows, int d, const float *z, const float *a, const float *gy, const float *gres,
                                const float *stats, float eps, float *gz, float *ga, float *gb, void *scratch,
                                long long scratch_bytes, void *stream);
+
+/* ------------------------------------ DGCNN's BatchNorm + ReLU + max over the neighbours, both ways (DCP training) */
+
+/* BatchNorm2d (batch or running statistics) -> ReLU -> max over the neighbour axis of z (b,c,k,n), neighbours on the slow
+ * axis and n contiguous (registration/models/dcp.py: DGCNN's stages; the reference composes conv, BatchNorm2d, ReLU and
+ * max, dcp.py:286-318, and autograd keeps the BatchNorm's and the ReLU's outputs).  M = b k n values per channel:
+ *   batch statistics:   mean_c = sum z / M,  var_c = sum (z - mean_c)^2 / M (biased, from CENTRED values),
+ *                       invstd_c = 1 / sqrt(var_c + eps)
+ *   running statistics: the caller fills stats with {running_mean_c, 1 / sqrt(running_var_c + eps)}
+ *   y = fmaf(z - mean_c, gamma_c * invstd_c, beta_c),   r = relu(y),   pooled[b,c,n] = max_j r[b,c,j,n],
+ *   arg[b,c,n] = the LOWEST j that attains it (uint8)
+ * ReLU keeps a NaN; the maximum is NaN if a member is, and arg is then the lowest j that holds a NaN (torch's CPU rule).
+ *
+ * mvp_edge_bn_stats: z -> stats (c,2) = {mean, invstd} and var (c) = the biased variance (what the running variance is
+ * updated from, times M / (M - 1)).  One workgroup per (b,c) slab of k n contiguous floats forms the slab's {mean, M2} in
+ * double, M2 from values centred on the slab's own mean (the slab stays in registers up to 20480 floats, longer ones are
+ * read twice); a second launch merges the b partials of a channel in ascending b with Chan's update, in double.  No
+ * atomics: the same bits on every run.  `scratch` holds mvp_edge_bn_scratch_bytes(b, c) bytes, 16-byte aligned.
+ *
+ * mvp_edge_bn_relu_max: z, stats, gamma (c), beta (c) -> r (b,c,k,n) or nothing (r == NULL: nothing of z's size is
+ * written), pooled (b,c,n), arg (b,c,n) uint8.  One workgroup per (b,c); a lane owns groups of four columns and walks k.
+ *
+ * Refusals, before anything is launched, in this order: MVP_EBADSHAPE for b < 1, c < 1, k outside 1..64, n < 4, n % 4 != 0,
+ * k n >= 2^31 or b c >= 2^31; MVP_EBADARG for eps negative or not finite, for z, r, g_r, gz, pooled or g_pool off a
+ * 16-byte address (arg: 4-byte), for a NULL required buffer and for scratch that is NULL, unaligned or too small.
+ *
+ * Non-finite values.  Batch statistics: a NaN or an Inf anywhere in a channel makes that channel's mean, invstd and var
+ * NaN, hence all of its r, pooled and gz; no other channel changes by a bit.  Running statistics: the map is elementwise,
+ * a NaN z[b,c,j,n] makes r[b,c,j,n] and pooled[b,c,n] NaN (an Inf gives y = +-Inf or, with gamma == 0, NaN) and nothing
+ * else; its gz is 0 (the mask y > 0 is false for a NaN).
+ * A dead channel (every y <= 0) gets r = 0, pooled = 0, arg = 0, gz = 0, ggamma = gbeta = 0, all exactly. */
+long long mvp_edge_bn_scratch_bytes(int b, int c);
+int mvp_edge_bn_stats(int b, int c, int k, int n, const float *z, float eps, float *stats, float *var, void *scratch,
+                      long long scratch_bytes, void *stream);
+int mvp_edge_bn_relu_max(int b, int c, int k, int n, const float *z, const float *stats, const float *gamma,
+                         const float *beta, float *r, float *pooled, unsigned char *arg, void *stream);
+
+/* Backward of the above from z, stats, gamma, beta and arg alone: r is no input, the ReLU mask is y > 0 with y recomputed by
+ * the forward's own expression (bit-identical).  g_r (b,c,k,n) and g_pool (b,c,n) are the gradients of r and pooled; either
+ * may be NULL (not both: MVP_EBADARG).
+ *   g_y = (g_r + [j == arg] g_pool) where y > 0, else 0
+ *   gbeta_c = sum g_y,   ggamma_c = sum g_y xhat,   xhat = (z - mean_c) invstd_c
+ *   batch_stats != 0:  gz = gamma_c invstd_c (g_y - gbeta_c / M - xhat ggamma_c / M)
+ *   batch_stats == 0:  gz = gamma_c invstd_c g_y
+ * Pass 1 leaves per-slab sums of g_y and g_y xhat (double) in scratch, a small launch adds a channel's b partials in
+ * ascending b and writes ggamma / gbeta (each may be NULL), pass 2 writes gz.  With running statistics and both sums
+ * unwanted pass 1 is skipped (and no scratch is needed).  No atomics, bit-reproducible.  Refusals as above. */
+int mvp_edge_bn_relu_max_backward(int b, int c, int k, int n, int batch_stats, const float *z, const float *stats,
+                                  const float *gamma, const float *beta, const unsigned char *arg, const float *g_r,
+                                  const float *g_pool, float *gz, float *ggamma, float *gbeta, void *scratch,
+                                  long long scratch_bytes, void *stream);
 
 /* ------------------------------------------- registration (DeepGMR) head */
 

@@ -67,11 +67,14 @@ SIGNATURES = {
     "mvp_gmm_params_backward": "iiippppppppp",
     "mvp_ref_layernorm": "iippppfppp",
     "mvp_ref_layernorm_backward": "iipppppfppppq",
+    "mvp_edge_bn_stats": "iiiipfpppq",
+    "mvp_edge_bn_relu_max": "iiiippppppp",
+    "mvp_edge_bn_relu_max_backward": "iiiiipppppppppppq",
 }
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "f": ctypes.c_float,
        "q": ctypes.c_longlong}
 
-ABI_VERSION = 23  # MVP_ABI_VERSION of include/mvpops.h this binding was written against
+ABI_VERSION = 24  # MVP_ABI_VERSION of include/mvpops.h this binding was written against
 
 # default of mvp_emd_configure's `split` knob (csrc/emd.hip: emd_knobs)
 EMD_DEFAULT_SPLIT = 5
@@ -127,6 +130,8 @@ def load():
     lib.mvp_dense_edge_conv_scratch_bytes.argtypes = [ctypes.c_int] * 5
     lib.mvp_ref_layernorm_backward_scratch_bytes.restype = ctypes.c_longlong
     lib.mvp_ref_layernorm_backward_scratch_bytes.argtypes = [ctypes.c_int] * 2
+    lib.mvp_edge_bn_scratch_bytes.restype = ctypes.c_longlong
+    lib.mvp_edge_bn_scratch_bytes.argtypes = [ctypes.c_int] * 2
     for name, sig in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype = ctypes.c_int
@@ -292,11 +297,17 @@ def ref_layernorm_backward_scratch_bytes(rows, d):
     return int(load().mvp_ref_layernorm_backward_scratch_bytes(int(rows), int(d)))
 
 
+def edge_bn_scratch_bytes(b, c):
+    """Scratch of mvp_edge_bn_stats and mvp_edge_bn_relu_max_backward (0: shape refused).  No GPU needed."""
+    return int(load().mvp_edge_bn_scratch_bytes(int(b), int(c)))
+
+
 def exported_symbols():
     """All entry points include/mvpops.h declares."""
     return ["mvp_abi_version", "mvp_last_hip_error", "mvp_emd_scratch_bytes", "mvp_emd_configure", "mvp_chamfer_scratch_bytes", "mvp_knn_scratch_bytes", "mvp_fps_scratch_bytes", "mvp_fps_cluster_scratch_bytes",
             "mvp_scatter_scratch_bytes", "mvp_pointwise_wgrad_scratch_bytes", "mvp_pointwise_wgrad_mfma_scratch_bytes",
             "mvp_pointwise_mfma_splitk_plan", "mvp_pointwise_mfma_splitk_scratch_bytes",
             "mvp_pointwise_max_backward_scratch_bytes", "mvp_share_gather_sum_lds_bytes",
-            "mvp_dense_edge_conv_scratch_bytes", "mvp_ref_layernorm_backward_scratch_bytes"] \
+            "mvp_dense_edge_conv_scratch_bytes", "mvp_ref_layernorm_backward_scratch_bytes",
+            "mvp_edge_bn_scratch_bytes"] \
         + list(SIGNATURES)

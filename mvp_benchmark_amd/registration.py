@@ -22,14 +22,17 @@ below s_2.  s_2 = s_3 with det H < 0 and rank <= 1 are poles of R itself: that
 sample's gradient is inf / NaN, the rest of the batch is unaffected.
 
 The DeepGMR pieces (rri_features, gmm_params, gmm_register) follow, then DCP's fused edge MLP (edge_mlp_max) and the
-transformer's LayerNorm with its residual sum (ref_layer_norm).
+transformer's LayerNorm with its residual sum (ref_layer_norm), then DGCNN's BatchNorm + ReLU + max over the neighbours
+for training (bn_relu_max).
 """
 import math
 
 import torch
+import torch.nn.functional as F
 from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
-from ._lib import call, ref_layernorm_backward_scratch_bytes
+from ._lib import call, edge_bn_scratch_bytes, ref_layernorm_backward_scratch_bytes
 
 
 def svd3_kabsch_backward(U, S, V, flipped, grad_R):
@@ -417,3 +420,130 @@ def ref_layer_norm(x, a, b, eps=1e-6, residual=None):
         return _layer_norm_reference(x, a, b, eps)
     z = x + residual
     return z, _layer_norm_reference(z, a, b, eps)
+
+
+# ------------------------------------------------------- DGCNN's BatchNorm + ReLU + max over the neighbours, both ways (DCP)
+# registration/models/dcp.py: DGCNN in training -- after each edge stage's 1x1 convolution, BatchNorm2d (batch or running
+# statistics), ReLU and the max over the k neighbours as kernels (mvp_edge_bn_stats, mvp_edge_bn_relu_max[_backward],
+# csrc/edge_bn.hip).  Saved for backward: z, two statistics per channel and one byte per pooled value; never r.
+
+EDGE_BN = False            # True: DGCNN.forward runs stages 1-4 through bn_relu_max when training or a gradient is needed
+
+
+def _bn_relu_max_reference(z, weight, bias, running_mean, running_var, training, momentum, eps, want_r=True):
+    """The composition in torch: F.batch_norm, relu, max(dim=2).  momentum None leaves the running statistics alone (a
+    cumulative average needs the caller's batch count)."""
+    y = F.batch_norm(z, running_mean, running_var, weight, bias, training, 0.0 if momentum is None else momentum, eps)
+    r = torch.relu(y)
+    return (r if want_r else None), r.max(dim=2)[0]
+
+
+def bn_relu_max_backward_reference(z, weight, bias, mean, invstd, arg, g_r, g_pool, batch_stats):
+    """The closed form mvp_edge_bn_relu_max_backward computes, in torch: z (B,C,k,N), mean / invstd (C), arg (B,C,N) the
+    neighbour each pooled value came from, g_r (B,C,k,N) or None, g_pool (B,C,N) or None -> (gz, ggamma, gbeta).
+        g_y = (g_r + [j == arg] g_pool) (y > 0),  gbeta = sum g_y,  ggamma = sum g_y xhat,  xhat = (z - mean) invstd
+        gz = gamma invstd (g_y - gbeta / M - xhat ggamma / M)   (running statistics: gamma invstd g_y)"""
+    v = lambda t: t.view(1, -1, 1, 1)
+    xhat = (z - v(mean)) * v(invstd)
+    y = xhat * v(weight) + v(bias)
+    g = torch.zeros_like(z) if g_r is None else g_r.clone()
+    if g_pool is not None:
+        g.scatter_add_(2, arg.long().unsqueeze(2), g_pool.unsqueeze(2))
+    g_y = torch.where(y > 0, g, torch.zeros_like(g))
+    gbeta, ggamma = g_y.sum(dim=(0, 2, 3)), (g_y * xhat).sum(dim=(0, 2, 3))
+    if not batch_stats:
+        return v(weight * invstd) * g_y, ggamma, gbeta
+    m = z.numel() // z.shape[1]
+    return v(weight * invstd) * (g_y - v(gbeta) / m - xhat * v(ggamma) / m), ggamma, gbeta
+
+
+def _bn_relu_max_fits(z, weight, bias, running_mean, running_var, training, momentum):
+    """Whether the kernels take these tensors as they are: float32 CUDA, contiguous, on 16-byte addresses, a shape the entry
+    points cover, and a way to the statistics (a batch of more than one value, or running statistics to read)."""
+    if z.dim() != 4 or weight is None or bias is None or not isinstance(momentum, float):
+        return False
+    b, c, k, n = z.shape
+    if not (b >= 1 and c >= 1 and 1 <= k <= 64 and n >= 4 and n % 4 == 0 and k * n < 2 ** 31 and b * c < 2 ** 31):
+        return False
+    running = (running_mean, running_var)
+    if any(t is None for t in running) and not (training and all(t is None for t in running)):
+        return False
+    if training and b * k * n < 2:
+        return False
+    tensors = [z, weight, bias] + [t for t in running if t is not None]
+    if not all(_on_op_layer(t) and t.is_contiguous() and t.device == z.device for t in tensors):
+        return False
+    return z.data_ptr() % 16 == 0 and all(t.shape == (c,) for t in tensors[1:])
+
+
+class BnReluMax(Function):
+    """(z (B,C,k,N), weight (C), bias (C), stats (C,2) = {mean, invstd} or None for batch statistics, eps, want_r) ->
+    (r or None, pooled (B,C,N), stats, var (C) biased or None): float32 CUDA only (bn_relu_max decides).  Saves z, weight,
+    bias, stats and arg (uint8), never r."""
+
+    @staticmethod
+    def forward(ctx, z, weight, bias, stats, eps, want_r):
+        b, c, k, n = z.shape
+        batch = stats is None
+        var = None
+        if batch:
+            stats = torch.empty(c, 2, device=z.device, dtype=torch.float32)
+            var = torch.empty(c, device=z.device, dtype=torch.float32)
+            nbytes = edge_bn_scratch_bytes(b, c)
+            scratch = torch.empty(nbytes, device=z.device, dtype=torch.uint8)
+            call("mvp_edge_bn_stats", z.device, b, c, k, n, z, eps, stats, var, scratch, nbytes)
+        r = torch.empty_like(z) if want_r else None
+        pooled = torch.empty(b, c, n, device=z.device, dtype=torch.float32)
+        arg = torch.empty(b, c, n, device=z.device, dtype=torch.uint8)
+        call("mvp_edge_bn_relu_max", z.device, b, c, k, n, z, stats, weight, bias, r, pooled, arg)
+        ctx.batch = batch
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(z, weight, bias, stats, arg)
+        if batch:
+            ctx.mark_non_differentiable(stats, var)
+        return r, pooled, (stats if batch else None), var
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_r, g_pool, _g_stats, _g_var):
+        z, weight, bias, stats, arg = ctx.saved_tensors
+        if g_r is None and g_pool is None:
+            return None, None, None, None, None, None
+        b, c, k, n = z.shape
+        g_r, g_pool = (None if g_r is None else _aligned_rows(g_r)), (None if g_pool is None else _aligned_rows(g_pool))
+        gz = torch.empty_like(z)
+        ggamma = torch.empty_like(weight) if ctx.needs_input_grad[1] else None
+        gbeta = torch.empty_like(bias) if ctx.needs_input_grad[2] else None
+        sums = ctx.batch or ggamma is not None or gbeta is not None
+        nbytes = edge_bn_scratch_bytes(b, c) if sums else 0
+        scratch = torch.empty(nbytes, device=z.device, dtype=torch.uint8) if sums else None
+        call("mvp_edge_bn_relu_max_backward", z.device, b, c, k, n, int(ctx.batch), z, stats, weight, bias, arg, g_r, g_pool,
+             gz, ggamma, gbeta, scratch, nbytes)
+        return (gz if ctx.needs_input_grad[0] else None), ggamma, gbeta, None, None, None
+
+
+def bn_relu_max(z, weight, bias, running_mean, running_var, training, momentum, eps, want_r=True):
+    """BatchNorm2d -> ReLU -> max over the neighbour axis of z (B,C,k,N): returns (r or None, pooled), r = relu(bn(z))
+    (B,C,k,N) -- None with want_r=False, and then nothing of z's size is written -- and pooled = r.max(dim=2) (B,C,N).
+    training: batch statistics (biased variance from centred values), and running_mean / running_var, where given, move as
+    nn.BatchNorm2d moves them: running = (1 - momentum) running + momentum {mean, var M / (M - 1)}, under no_grad; the
+    caller increments num_batches_tracked.  Otherwise the running statistics normalise.  ReLU keeps a NaN, the maximum is
+    NaN if a member is; of equal maxima the lowest neighbour takes the gradient.
+    float32 CUDA contiguous tensors with N % 4 == 0, k <= 64 and a float momentum run mvp_edge_bn_stats,
+    mvp_edge_bn_relu_max and, for gradients to z, weight and bias, mvp_edge_bn_relu_max_backward; CPU tensors, float64,
+    momentum None, any other shape or an unaligned view take the composition written in torch."""
+    if not _bn_relu_max_fits(z, weight, bias, running_mean, running_var, training, momentum):
+        return _bn_relu_max_reference(z, weight, bias, running_mean, running_var, training, momentum, eps, want_r)
+    eps = float(eps)
+    if training:
+        r, pooled, stats, var = BnReluMax.apply(z, weight, bias, None, eps, want_r)
+        if running_mean is not None:
+            m = z.numel() // z.shape[1]
+            with torch.no_grad():
+                running_mean.mul_(1 - momentum).add_(stats[:, 0], alpha=momentum)
+                running_var.mul_(1 - momentum).add_(var, alpha=momentum * m / (m - 1))
+        return r, pooled
+    with torch.no_grad():
+        stats = torch.stack((running_mean, (1 / torch.sqrt(running_var.double() + eps)).float()), dim=1).contiguous()
+    r, pooled, _, _ = BnReluMax.apply(z, weight, bias, stats, eps, want_r)
+    return r, pooled

@@ -14,6 +14,8 @@ the 1x1 convolutions are library GEMMs -- except on DGCNN's opt-in inference rou
 (mvp_benchmark_amd.registration.EDGE_MLP), which runs the four edge stages and their
 maxima as one kernel and conv5 as one MFMA GEMM.  The transformer's LayerNorm and residual sums have an opt-in route of
 their own (mvp_benchmark_amd.registration.LAYER_NORM): every `x + f(...)` followed by a norm is one kernel, each way.
+DGCNN in training has a third (mvp_benchmark_amd.registration.EDGE_BN): BatchNorm, ReLU and the max over the neighbours of
+stages 1-4 as kernels, forward and backward.
 """
 import copy
 import math
@@ -228,6 +230,26 @@ class DGCNN(nn.Module):
         w5 = self.conv5.weight.view(widths[4], -1) * scales[4].unsqueeze(1)
         return _pw.mfma_linear(pooled, w5.contiguous(), bias=shifts[4].contiguous(), relu=True)
 
+    def _edge_bn(self, x):
+        """Whether stages 1-4 run BatchNorm, ReLU and the max as kernels (mvp_benchmark_amd.registration.bn_relu_max): the
+        switch is on, x is float32 CUDA, the module trains or some gradient is needed (eval without gradients stays
+        composed, or EDGE_MLP's), and every BatchNorm tracks its running statistics with a float momentum."""
+        if not _reg.EDGE_BN or not (x.is_cuda and x.dtype == torch.float32) or x.dim() != 3:
+            return False
+        if not (self.training or (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())))):
+            return False
+        bns = [getattr(self, "bn%d" % i) for i in range(1, 5)]
+        return all(bn.track_running_stats and bn.running_mean is not None and isinstance(bn.momentum, float) for bn in bns)
+
+    def _stage_edge_bn(self, i, edge, want_r):
+        """conv_i, then BatchNorm + ReLU + max over k in one operator -> (relu(bn(conv(edge))) or None, its maximum (B,C,N));
+        num_batches_tracked counts as nn.BatchNorm2d counts it."""
+        bn = getattr(self, "bn%d" % i)
+        z = getattr(self, "conv%d" % i)(edge)
+        if bn.training:
+            bn.num_batches_tracked.add_(1)
+        return _reg.bn_relu_max(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.training, bn.momentum, bn.eps, want_r)
+
     def forward(self, x):
         if self._fused(x):
             return self._forward_fused(x.detach())
@@ -236,9 +258,14 @@ class DGCNN(nn.Module):
         # 1x1 convolutions + per-channel BatchNorm: layout-agnostic; the reference keeps (B, 6, N, 20))
         edge = get_graph_feature(x, k_major=True)
         pooled = []
+        fused_bn = self._edge_bn(x)
         for i in range(1, 5):
-            edge = self._stage(i, edge)
-            pooled.append(edge.max(dim=2, keepdim=True)[0])           # (B, C, 1, N)
+            if fused_bn:                                              # stage 4's activations feed only their maximum
+                edge, top = self._stage_edge_bn(i, edge, want_r=i < 4)
+                pooled.append(top.unsqueeze(2))
+            else:
+                edge = self._stage(i, edge)
+                pooled.append(edge.max(dim=2, keepdim=True)[0])       # (B, C, 1, N)
         return self._stage(5, torch.cat(pooled, dim=1)).view(batch_size, -1, num_points)
 
 

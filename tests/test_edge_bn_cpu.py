@@ -1,0 +1,267 @@
+"""Host side of the fused BatchNorm + ReLU + max (no GPU): the binding, the wrapper's composed route on CPU / float64 tensors
+against a real nn.BatchNorm2d, the closed-form backward against autograd, the lowest-j tie rule, the entry points' refusals
+through the loaded library, the model switch falling back on the CPU, and the bounds of tests/edge_bn_cases.py checked on
+the float32 torch composition (met) and on wrong variants (missed by far), so the GPU tests' bounds are neither vacuous nor
+out of reach."""
+import copy
+import ctypes
+import importlib.util
+import os
+import types
+
+import pytest
+import torch
+import torch.nn.functional as F
+from conftest import ROOT
+
+import edge_bn_cases as cases
+
+OK, EBADSHAPE, EBADARG = 0, -1, -2
+
+
+def _dcp():
+    spec = importlib.util.spec_from_file_location("registration_dcp_edge_bn_cpu", os.path.join(ROOT, "registration", "models", "dcp.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def _inputs(shape, seed=0, dtype=torch.float64):
+    gen = torch.Generator().manual_seed(seed)
+    r = lambda *s: torch.randn(*s, generator=gen, dtype=dtype)
+    B, C, k, N = shape
+    return {"z": r(B, C, k, N) + 0.5, "gamma": r(C), "beta": 0.5 * r(C), "g_r": r(B, C, k, N), "g_pool": r(B, C, N),
+            "rm": 0.5 + 0.1 * r(C), "rv": 0.5 + torch.rand(C, generator=gen, dtype=dtype)}
+
+
+def test_binding_lists_the_entry_points():
+    from mvp_benchmark_amd import _lib
+    assert _lib.ABI_VERSION >= 24
+    assert _lib.SIGNATURES["mvp_edge_bn_stats"] == "iiiipfpppq"
+    assert _lib.SIGNATURES["mvp_edge_bn_relu_max"] == "iiiippppppp"
+    assert _lib.SIGNATURES["mvp_edge_bn_relu_max_backward"] == "iiiii" + "p" * 11 + "q"
+    symbols = _lib.exported_symbols()
+    lib = _lib.load()
+    for name in ("mvp_edge_bn_scratch_bytes", "mvp_edge_bn_stats", "mvp_edge_bn_relu_max", "mvp_edge_bn_relu_max_backward"):
+        assert name in symbols and hasattr(lib, name), name
+
+
+def test_switch_defaults_to_off():
+    from mvp_benchmark_amd import registration
+    assert registration.EDGE_BN is False
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32], ids=str)
+@pytest.mark.parametrize("training", [True, False])
+def test_wrapper_on_the_cpu_equals_a_real_batchnorm(dtype, training):
+    from mvp_benchmark_amd.registration import bn_relu_max
+    d = _inputs((3, 5, 7, 12), seed=1, dtype=dtype)
+    bn = torch.nn.BatchNorm2d(5).to(dtype)
+    with torch.no_grad():
+        bn.weight.copy_(d["gamma"]), bn.bias.copy_(d["beta"]), bn.running_mean.copy_(d["rm"]), bn.running_var.copy_(d["rv"])
+    mine = copy.deepcopy(bn)
+    bn.train(training), mine.train(training)
+    want_r = torch.relu(bn(d["z"]))
+    if training:
+        mine.num_batches_tracked.add_(1)                             # the caller's part
+    r, pooled = bn_relu_max(d["z"], mine.weight, mine.bias, mine.running_mean, mine.running_var, training, mine.momentum, mine.eps)
+    assert torch.equal(r, want_r) and torch.equal(pooled, want_r.max(dim=2)[0])
+    assert torch.equal(mine.running_mean, bn.running_mean) and torch.equal(mine.running_var, bn.running_var)
+    assert int(mine.num_batches_tracked) == int(bn.num_batches_tracked) == (1 if training else 0)
+    assert training == (not torch.equal(bn.running_mean, d["rm"]))   # ... and they moved only in training
+    none, pooled2 = bn_relu_max(d["z"], mine.weight, mine.bias, None, None, True, mine.momentum, mine.eps, want_r=False)
+    assert none is None and (not training or torch.equal(pooled2, pooled))
+    # momentum None: the composition, the running statistics left alone
+    before = mine.running_mean.clone()
+    r3, _ = bn_relu_max(d["z"], mine.weight, mine.bias, mine.running_mean, mine.running_var, training, None, mine.eps)
+    assert torch.equal(r3, want_r) and torch.equal(mine.running_mean, before)
+
+
+@pytest.mark.parametrize("training", [True, False])
+@pytest.mark.parametrize("grads", ["g_r", "g_pool", "both"])
+def test_gradcheck(training, grads):
+    from mvp_benchmark_amd.registration import bn_relu_max
+    d = _inputs((2, 2, 3, 4), seed=2)
+    z, gamma, beta = (d[k].clone().requires_grad_() for k in ("z", "gamma", "beta"))
+
+    def fn(z, gamma, beta):
+        r, pooled = bn_relu_max(z, gamma, beta, d["rm"].clone(), d["rv"].clone(), training, 0.1, cases.EPS)
+        return {"g_r": (r,), "g_pool": (pooled,), "both": (r, pooled)}[grads]
+    assert torch.autograd.gradcheck(fn, (z, gamma, beta))
+
+
+@pytest.mark.parametrize("shape", [(2, 2, 3, 4), (3, 5, 7, 12), (1, 1, 1, 4), (2, 3, 20, 8)], ids=str)
+@pytest.mark.parametrize("training", [True, False])
+@pytest.mark.parametrize("grads", ["g_r", "g_pool", "both"])
+def test_closed_form_backward_matches_autograd(shape, training, grads):
+    from mvp_benchmark_amd.registration import bn_relu_max_backward_reference
+    d = _inputs(shape, seed=3 + sum(shape))
+    z, gamma, beta = (d[k].clone().requires_grad_() for k in ("z", "gamma", "beta"))
+    r, pooled, arg = cases.compose(z, gamma, beta, d["rm"].clone(), d["rv"].clone(), training)
+    g_r = d["g_r"] if grads != "g_pool" else None
+    g_pool = d["g_pool"] if grads != "g_r" else None
+    outs, gs = zip(*[(o, g) for o, g in ((r, g_r), (pooled, g_pool)) if g is not None])
+    want = torch.autograd.grad(outs, (z, gamma, beta), gs)
+    ref = cases.reference(z, gamma, beta, running=None if training else (d["rm"], d["rv"]))
+    got = bn_relu_max_backward_reference(z.detach(), gamma.detach(), beta.detach(), ref["mean"], ref["invstd"], arg, g_r, g_pool, training)
+    mine = cases.reference_backward(ref, r.detach() > 0, arg, g_r, g_pool)          # ... and the tests' own reference
+    for g, w, name in zip(got, want, ("gz", "ggamma", "gbeta")):
+        scale = max(1.0, float(w.abs().max()))
+        assert float((g - w).abs().max()) <= 1e-12 * scale, name
+        assert float((mine[name] - w).abs().max()) <= 1e-12 * scale, name
+
+
+def test_ties_go_to_the_lowest_neighbour():
+    """Duplicated neighbours: torch's CPU max takes the first of equal maxima, and so does the closed form's scatter."""
+    from mvp_benchmark_amd.registration import bn_relu_max, bn_relu_max_backward_reference
+    d = _inputs((2, 3, 6, 8), seed=5)
+    z = d["z"].clone()
+    z[:, :, 4] = z[:, :, 1]
+    z[:, :, 5] = z[:, :, 1]
+    z[:, :, 3] = z[:, :, 0]
+    z.requires_grad_()
+    r, pooled = bn_relu_max(z, d["gamma"], d["beta"], None, None, True, 0.1, cases.EPS)
+    arg = r.max(dim=2)[1]
+    top = (r == pooled.unsqueeze(2))
+    lowest = top.int().argmax(dim=2)                                   # the first True along k
+    assert torch.equal(arg, lowest) and int(top.sum(dim=2).max()) >= 3 and int(arg.max()) <= 2
+    pooled.backward(d["g_pool"])
+    ref = cases.reference(z, d["gamma"], d["beta"])
+    gz, _, _ = bn_relu_max_backward_reference(z.detach(), d["gamma"], d["beta"], ref["mean"], ref["invstd"], lowest, None, d["g_pool"], True)
+    assert float((z.grad - gz).abs().max()) <= 1e-12 * float(gz.abs().max())
+
+
+def test_refusals_need_no_gpu():
+    from mvp_benchmark_amd import _lib
+    lib = _lib.load()
+    null, dummy, odd, odd2 = ctypes.c_void_p(0), ctypes.c_void_p(4096), ctypes.c_void_p(4100), ctypes.c_void_p(4098)
+    eps = ctypes.c_float(1e-5)
+    big = 1 << 40
+    stats = lambda b, c, k, n, p=null, e=eps, **kw: lib.mvp_edge_bn_stats(
+        b, c, k, n, kw.get("z", p), e, p, p, kw.get("scratch", p), kw.get("nbytes", big), null)
+    fwd = lambda b, c, k, n, p=null, e=None, **kw: lib.mvp_edge_bn_relu_max(
+        b, c, k, n, kw.get("z", p), p, p, p, kw.get("r", p), kw.get("pooled", p), kw.get("arg", p), null)
+    bwd = lambda b, c, k, n, p=null, e=None, **kw: lib.mvp_edge_bn_relu_max_backward(
+        b, c, k, n, kw.get("batch", 1), kw.get("z", p), p, p, p, kw.get("arg", p), kw.get("g_r", p), kw.get("g_pool", p),
+        kw.get("gz", p), kw.get("ggamma", p), kw.get("gbeta", p), kw.get("scratch", p), kw.get("nbytes", big), null)
+    for fn in (stats, fwd, bwd):
+        for dims in ((0, 3, 20, 8), (-1, 3, 20, 8), (2, 0, 20, 8), (2, 3, 0, 8), (2, 3, 65, 8), (2, 3, 20, 0), (2, 3, 20, 2),
+                     (2, 3, 20, 6), (2, 3, 20, 1022), (2, 3, 64, 2 ** 25), (65536, 32768, 1, 4)):
+            assert fn(*dims) == EBADSHAPE and fn(*dims, dummy) == EBADSHAPE, dims
+        for dims in ((1, 1, 1, 4), (2, 3, 64, 8), (128, 256, 20, 1024), (2, 3, 32, 2 ** 25), (32768, 65535, 1, 4)):
+            assert fn(*dims) == EBADARG, dims                               # covered: the null buffers are what is wrong
+    for bad in (-1e-6, float("nan"), float("inf")):
+        assert stats(2, 3, 20, 8, dummy, ctypes.c_float(bad)) == EBADARG
+    # a pointer off the 16-byte grid (arg: off the 4-byte grid), before anything else about the buffers
+    assert stats(2, 3, 20, 8, dummy, z=odd) == EBADARG
+    for name in ("z", "r", "pooled"):
+        assert fwd(2, 3, 20, 8, dummy, **{name: odd}) == EBADARG, name
+    assert fwd(2, 3, 20, 8, dummy, arg=odd2) == EBADARG
+    for name in ("z", "g_r", "g_pool", "gz"):
+        assert bwd(2, 3, 20, 8, dummy, **{name: odd}) == EBADARG, name
+    assert bwd(2, 3, 20, 8, dummy, arg=odd2) == EBADARG
+    assert bwd(2, 3, 20, 8, dummy, g_r=null, g_pool=null) == EBADARG        # both gradients absent
+    # scratch: [b c][2] double + [c][2] float rounded up to 16 bytes; 0 for a refused shape
+    need = _lib.edge_bn_scratch_bytes(2, 3)
+    assert need == 2 * 3 * 16 + 32 and _lib.edge_bn_scratch_bytes(128, 256) == 128 * 256 * 16 + 256 * 8
+    assert _lib.edge_bn_scratch_bytes(0, 3) == 0 and _lib.edge_bn_scratch_bytes(65536, 32768) == 0
+    for fn in (stats, bwd):
+        assert fn(2, 3, 20, 8, dummy, nbytes=need - 1) == EBADARG
+        assert fn(2, 3, 20, 8, dummy, scratch=null, nbytes=need) == EBADARG
+        assert fn(2, 3, 20, 8, dummy, scratch=odd, nbytes=need) == EBADARG
+    # running statistics with neither sum wanted need none, batch statistics always do; nothing is launched here: the
+    # refusal that answers is the one asked for
+    assert bwd(2, 3, 20, 8, dummy, batch=0, ggamma=dummy, scratch=null, nbytes=0) == EBADARG
+
+
+def _variants(z, gamma, beta, eps):
+    """Wrong formulas for y in float64 (only the formula differs), the one-pass variance with its float32 moments."""
+    M = z.numel() // z.shape[1]
+    mean = z.mean(dim=(0, 2, 3), keepdim=True)
+    c = z - mean
+    var = (c * c).mean(dim=(0, 2, 3), keepdim=True)
+    g, b = gamma.view(1, -1, 1, 1), beta.view(1, -1, 1, 1)
+    z32 = z.float()
+    one_pass = ((z32 * z32).mean(dim=(0, 2, 3), keepdim=True) - z32.mean(dim=(0, 2, 3), keepdim=True) ** 2).clamp_min(0).double()
+    return {"one-pass variance": c / torch.sqrt(one_pass + eps) * g + b,
+            "unbiased batch variance": c / torch.sqrt(var * M / (M - 1) + eps) * g + b,
+            "eps outside the root": c / (torch.sqrt(var) + eps) * g + b}
+
+
+@pytest.mark.parametrize("shape", [(2, 2, 3, 4), (2, 3, 20, 8), (3, 5, 7, 68), (2, 8, 20, 260)], ids=str)
+@pytest.mark.parametrize("family", cases.FAMILIES, ids=str)
+def test_float32_composition_meets_the_bounds(shape, family):
+    """The parent's route, float32 torch on the CPU, in both statistics modes, against the float64 reference with the
+    composition's own mask and arg."""
+    case = cases.make_case(shape, family)
+    for training in (True, False):
+        z, gamma, beta = (case[k].clone().requires_grad_() for k in ("z", "gamma", "beta"))
+        rm, rv = case["running_mean"].clone(), case["running_var"].clone()
+        r, pooled, arg = cases.compose(z, gamma, beta, rm, rv, training)
+        ref = cases.reference(z, gamma, beta, running=None if training else (case["running_mean"], case["running_var"]))
+        s_r = cases.share(r, ref["r"], ref["mag_y"], 1)
+        gz, ggamma, gbeta = torch.autograd.grad((r, pooled), (z, gamma, beta), (case["g_r"], case["g_pool"]))
+        back = cases.reference_backward(ref, r.detach() > 0, arg, case["g_r"], case["g_pool"])
+        s = {"r": s_r, "gz": cases.share(gz, back["gz"], back["mag_gz"], 1),
+             "ggamma": cases.share(ggamma, back["ggamma"], back["mag_ggamma"], 1),
+             "gbeta": cases.share(gbeta, back["gbeta"], back["mag_gbeta"], 1)}
+        print("float32 composition %s %s %s: %s of u * mag; sum|g_y| / sum|g_y xhat| <= %.2f" % (
+            shape, family, "batch" if training else "running", {k: round(v, 3) for k, v in s.items()}, back["abs_ratio"]))
+        assert s["r"] <= cases.T_Y and s["gz"] <= cases.T_GZ and s["ggamma"] <= cases.T_GGAMMA and s["gbeta"] <= cases.T_GBETA, s
+        if training:                                                        # the running statistics moved as nn.BatchNorm2d's
+            M = ref["M"]
+            want_mean = 0.9 * case["running_mean"].double() + 0.1 * ref["mean"]
+            want_var = 0.9 * case["running_var"].double() + 0.1 * ref["var"] * M / (M - 1)
+            assert cases.share(rm, want_mean, case["running_mean"].double().abs() + ref["mag_mean"], 4) <= 1.0
+            assert cases.share(rv, want_var, case["running_var"].double() + ref["mag_var"] * M / (M - 1), 4) <= 1.0
+
+
+def test_wrong_variants_miss_the_bounds_by_far():
+    """Each wrong variant, in the family that exposes it, is at least 100 times outside the bound it is held to."""
+    worst = {}
+    for family in cases.FAMILIES:
+        for shape in ((2, 3, 20, 8), (3, 5, 7, 68), (2, 8, 20, 260)):
+            case = cases.make_case(shape, family)
+            z, gamma, beta = case["z"].double(), case["gamma"].double(), case["beta"].double()
+            ref = cases.reference(z, gamma, beta)
+            for name, y in _variants(z, gamma, beta, cases.EPS).items():
+                worst[name] = max(worst.get(name, 0.0), cases.share(y, ref["y"], ref["mag_y"], cases.T_Y))
+            mask, arg = ref["y"] > 0, ref["r"].max(dim=2)[1]
+            back = cases.reference_backward(ref, mask, arg, case["g_r"], case["g_pool"])
+            w = (gamma * ref["invstd"]).view(1, -1, 1, 1)
+            no_mean = w * (back["g_y"] - ref["xhat"] * back["ggamma"].view(1, -1, 1, 1) / ref["M"])
+            worst["gz without the mean term"] = max(worst.get("gz without the mean term", 0.0),
+                                                    cases.share(no_mean, back["gz"], back["mag_gz"], cases.T_GZ))
+            g = case["g_r"].double().clone()
+            g.scatter_add_(2, arg.unsqueeze(2), case["g_pool"].double().unsqueeze(2))
+            by_g = cases.reference_backward(ref, g > 0, arg, case["g_r"], case["g_pool"])
+            # the mask enters mag as well: hold the wrong gz to the right bound wherever that bound is not 0
+            err = (by_g["gz"] - back["gz"]).abs() / (cases.T_GZ * cases.U * back["mag_gz"]).clamp_min(1e-300)
+            worst["mask from g"] = max(worst.get("mask from g", 0.0), float(err[back["mag_gz"] > 0].max()))
+    print(worst)
+    assert len(worst) == 5 and all(v >= 100 for v in worst.values()), worst
+
+
+def test_cpu_model_with_the_switch_on_equals_the_switch_off(monkeypatch):
+    """The kernels are float32 CUDA only: on the CPU the switch changes nothing, outputs, gradients and buffers are the
+    same bits."""
+    dcp = _dcp()
+    from mvp_benchmark_amd import registration
+    torch.manual_seed(6)
+    proto = dcp.DGCNN().train()
+    gen = torch.Generator().manual_seed(7)
+    x = torch.rand(2, 3, 32, generator=gen)
+    runs = {}
+    for on in (False, True):
+        monkeypatch.setattr(registration, "EDGE_BN", on)
+        net = copy.deepcopy(proto)
+        out = net(x)
+        out.square().mean().backward()
+        with torch.no_grad():
+            ev = net.eval()(x)
+        runs[on] = ([out.detach(), ev], {k: p.grad.clone() for k, p in net.named_parameters()}, {k: v.clone() for k, v in net.state_dict().items()})
+    assert all(torch.equal(u, v) for u, v in zip(runs[True][0], runs[False][0]))
+    for part in (1, 2):
+        assert runs[True][part].keys() == runs[False][part].keys()
+        assert all(torch.equal(runs[True][part][k], runs[False][part][k]) for k in runs[True][part])
+    assert int(runs[True][2]["bn1.num_batches_tracked"]) == 1

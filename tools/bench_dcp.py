@@ -3,7 +3,9 @@ backward (training step without the optimizer) timings, with the op-layer split 
 (kNN graph, neighbour gather / its gradient, the 3x3 Kabsch SVD launch); then the same-process A/B of the fused edge MLP
 (mvp_benchmark_amd.registration.EDGE_MLP) on the eval forward, on emb_nn alone and on the edge stages alone; then the same for
 the transformer's fused LayerNorm + residual sums (mvp_benchmark_amd.registration.LAYER_NORM): eval forward, forward + backward,
-the transformer alone, the training step's peak memory per route, and the two kernels alone with their bytes/s.
+the transformer alone, the training step's peak memory per route, and the two kernels alone with their bytes/s; then DGCNN's
+BatchNorm + ReLU + max over the neighbours as kernels in training (mvp_benchmark_amd.registration.EDGE_BN): emb_nn forward +
+backward, the whole step, peak memory per route, and the three entry points alone at the four stage shapes.
    python tools/bench_dcp.py            (MVP_BENCH_REPS: timed repetitions, MVP_BENCH_AB_ROUNDS: alternations, at least 5)"""
 import os, sys, time, types
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -222,3 +224,89 @@ for name, passes, fn in kernels:
     rate = passes * tensor_bytes / t / 1e9                                  # TB/s: bytes / ms / 1e9
     print("  %-70s %7.3f ms  %5.2f TB/s = %4.1f %% of spec, %4.1f %% of the copy rate" % (
         name, t, rate, rate / HBM_SPEC * 100, rate / HBM_COPY * 100), flush=True)
+
+# ---- DGCNN's BatchNorm + ReLU + max over k as kernels in training (mvp_benchmark_amd.registration.EDGE_BN, default off): the
+# two routes in this one process, alternated like the blocks above, every other switch off: emb_nn forward + backward on both
+# clouds, the whole training step; the step's peak memory per route; then the three entry points alone at cfg 5's four stage
+# shapes, bytes/s from the algorithmic bytes (T = one (B, C, k, N) tensor; pooled, arg and the statistics are under T / 16).
+del xs, ds_, gys, grs, zs, ys, gzs, scr
+torch.cuda.empty_cache()
+
+
+def emb_train():
+    emb.zero_grad(set_to_none=True)
+    (emb(clouds[0]).sum() + emb(clouds[1]).sum()).backward()
+
+
+net.train()
+print("# fused BatchNorm + ReLU + max A/B (training): %d alternations x %d repetitions, median ms [min .. max]; 4 stages x 2 "
+      "clouds over (%d, C, %d, %d), C = 64, 64, 128, 256" % (ROUNDS, REPS, B, K_GRAPH, N), flush=True)
+faster = {}
+for name, fn in (("emb_nn forward + backward, both clouds", emb_train), ("forward + backward", fwd_bwd)):
+    ms = {False: [], True: []}
+    for _ in range(ROUNDS):
+        for on in (False, True):
+            reg_ops.EDGE_BN = on
+            try:
+                ms[on].append(timed(fn))
+            finally:
+                reg_ops.EDGE_BN = False
+    med = {on: sorted(v)[len(v) // 2] for on, v in ms.items()}
+    faster[name] = all(f < c for f, c in zip(ms[True], ms[False]))
+    print("  %-40s composed %7.2f [%7.2f .. %7.2f]   fused %7.2f [%7.2f .. %7.2f]   composed - fused %6.2f ms   composed / "
+          "fused %.3f   fused faster in every alternation: %s" % (
+              name, med[False], min(ms[False]), max(ms[False]), med[True], min(ms[True]), max(ms[True]),
+              med[False] - med[True], med[False] / med[True], "yes" if faster[name] else "NO"), flush=True)
+peak = {}
+for on in (False, True):
+    reg_ops.EDGE_BN = on
+    try:
+        fwd_bwd(); torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        fwd_bwd(); torch.cuda.synchronize()
+        peak[on] = torch.cuda.max_memory_allocated() / 1e9
+        print("  training step, %s route: torch.cuda.max_memory_allocated %.2f GB" % ("fused" if on else "composed", peak[on]), flush=True)
+    finally:
+        reg_ops.EDGE_BN = False
+print("  criterion (fused faster than composed in every alternation of forward + backward, and a lower peak): %s" % (
+    "met" if faster["forward + backward"] and peak[True] < peak[False] else "NOT met -- the switch stays off either way"), flush=True)
+net.zero_grad(set_to_none=True)
+torch.cuda.empty_cache()
+
+print("# the entry points alone at (%d, C, %d, %d) float32; bytes/s from the algorithmic bytes; HBM %.1f TB/s spec, %.2f TB/s "
+      "measured float4 copy" % (B, K_GRAPH, N, HBM_SPEC, HBM_COPY), flush=True)
+ge = torch.Generator().manual_seed(7)
+for C, which in ((64, "stages 1 and 2"), (128, "stage 3"), (256, "stage 4")):
+    ze = (torch.randn(B, C, K_GRAPH, N, generator=ge) + 0.5).to(dev)
+    gre = torch.randn(B, C, K_GRAPH, N, generator=ge).to(dev)
+    gpe = torch.randn(B, C, N, generator=ge).to(dev)
+    gam, bet = torch.randn(C, generator=ge).to(dev), torch.randn(C, generator=ge).to(dev)
+    re_, gze = torch.empty_like(ze), torch.empty_like(ze)
+    pe, ae = torch.empty(B, C, N, device=dev), torch.empty(B, C, N, device=dev, dtype=torch.uint8)
+    ste, vae = torch.empty(C, 2, device=dev), torch.empty(C, device=dev)
+    gga, gbe = torch.empty(C, device=dev), torch.empty(C, device=dev)
+    nbe = _lib.edge_bn_scratch_bytes(B, C)
+    sce = torch.empty(nbe, device=dev, dtype=torch.uint8)
+    dims = (B, C, K_GRAPH, N)
+    T = ze.numel() * 4
+    _lib.call("mvp_edge_bn_stats", dev, *dims, ze, 1e-5, ste, vae, sce, nbe)
+    _lib.call("mvp_edge_bn_relu_max", dev, *dims, ze, ste, gam, bet, None, pe, ae)
+    entries = (
+        ("mvp_edge_bn_stats (1 read)", 1, lambda: _lib.call("mvp_edge_bn_stats", dev, *dims, ze, 1e-5, ste, vae, sce, nbe)),
+        ("mvp_edge_bn_relu_max, r written (1 read + 1 write)", 2,
+         lambda: _lib.call("mvp_edge_bn_relu_max", dev, *dims, ze, ste, gam, bet, re_, pe, ae)),
+        ("mvp_edge_bn_relu_max, no r (1 read)", 1,
+         lambda: _lib.call("mvp_edge_bn_relu_max", dev, *dims, ze, ste, gam, bet, None, pe, ae)),
+        ("mvp_edge_bn_relu_max_backward, g_r + g_pool, batch (4 reads + 1 write)", 5,
+         lambda: _lib.call("mvp_edge_bn_relu_max_backward", dev, *dims, 1, ze, ste, gam, bet, ae, gre, gpe, gze, gga, gbe, sce, nbe)),
+        ("mvp_edge_bn_relu_max_backward, g_pool only, batch (2 reads + 1 write)", 3,
+         lambda: _lib.call("mvp_edge_bn_relu_max_backward", dev, *dims, 1, ze, ste, gam, bet, ae, None, gpe, gze, gga, gbe, sce, nbe)),
+    )
+    print("  C = %d (%s), T = %.0f MB" % (C, which, T / 1e6), flush=True)
+    for name, passes, fn in entries:
+        t = sorted(timed(fn, 10) for _ in range(5))[2]
+        rate = passes * T / t / 1e9
+        print("    %-74s %7.3f ms  %5.2f TB/s = %4.1f %% of spec, %4.1f %% of the copy rate" % (
+            name, t, rate, rate / HBM_SPEC * 100, rate / HBM_COPY * 100), flush=True)
+    del ze, gre, gpe, re_, gze
+    torch.cuda.empty_cache()
