@@ -1,4 +1,12 @@
-"""Batched Kabsch / Procrustes rotation for the DCP registration head.
+"""The registration models' op layer: what registration/models/{dcp,deepgmr}.py run on HIP kernels, each with the same
+composition written in torch for CPU / float64 tensors (the float64 equivalence tests run on it).  In file order:
+
+  Kabsch rotation      kabsch_rotation, svd3, svd3_kabsch_backward             mvp_kabsch_svd3
+  DeepGMR              rri_features, gmm_params, gmm_register                  mvp_rri_features, mvp_gmm_params[_backward]
+  DCP's switches       EDGE_MLP, LAYER_NORM, EDGE_BN (all off) and routes(), the one way to flip them for a block
+  DGCNN, inference     edge_mlp_max                                            mvp_edge_mlp_max
+  the transformer      ref_layer_norm (LayerNorm + the residual sum)           mvp_ref_layernorm[_backward]
+  DGCNN, training      bn_relu_max (BatchNorm + ReLU + max over k)             mvp_edge_bn_stats, mvp_edge_bn_relu_max[_backward]
 
 `kabsch_rotation(H)` replaces the per-sample loop of the reference's SVDHead
 (registration/models/dcp.py:360-373, registration/model_utils.py:229-240):
@@ -20,11 +28,8 @@ smallest singular values do not cancel: every H with det H > 0 down to rank 2,
 coinciding singular values included, and every H with det H < 0 whose s_3 stays
 below s_2.  s_2 = s_3 with det H < 0 and rank <= 1 are poles of R itself: that
 sample's gradient is inf / NaN, the rest of the batch is unaffected.
-
-The DeepGMR pieces (rri_features, gmm_params, gmm_register) follow, then DCP's fused edge MLP (edge_mlp_max) and the
-transformer's LayerNorm with its residual sum (ref_layer_norm), then DGCNN's BatchNorm + ReLU + max over the neighbours
-for training (bn_relu_max).
 """
+import contextlib
 import math
 
 import torch
@@ -62,20 +67,24 @@ def svd3_kabsch_backward(U, S, V, flipped, grad_R):
     return U @ G @ V.transpose(1, 2)
 
 
+def _svd3_launch(H):
+    """One mvp_kabsch_svd3 launch on H (B,3,3) -> (U, S, V, R, flipped), float32 (flipped int32)."""
+    H = H.contiguous().float()
+    b = H.shape[0]
+    R, U, V = torch.empty_like(H), torch.empty_like(H), torch.empty_like(H)
+    S = torch.empty(b, 3, device=H.device, dtype=torch.float32)
+    flipped = torch.empty(b, device=H.device, dtype=torch.int32)
+    call("mvp_kabsch_svd3", H.device, b, H, R, U, S, V, flipped)
+    return U, S, V, R, flipped
+
+
 class KabschSVD(Function):
     """H (B,3,3) float32 CUDA -> R (B,3,3): mvp_kabsch_svd3."""
 
     @staticmethod
     def forward(ctx, H):
         assert H.dim() == 3 and H.shape[1:] == (3, 3)
-        H = H.contiguous().float()
-        b = H.shape[0]
-        R = torch.empty_like(H)
-        U = torch.empty_like(H)
-        V = torch.empty_like(H)
-        S = torch.empty(b, 3, device=H.device, dtype=torch.float32)
-        flipped = torch.empty(b, device=H.device, dtype=torch.int32)
-        call("mvp_kabsch_svd3", H.device, b, H, R, U, S, V, flipped)
+        U, S, V, R, flipped = _svd3_launch(H)
         ctx.save_for_backward(U, S, V, flipped)
         return R
 
@@ -91,13 +100,7 @@ kabsch_rotation = KabschSVD.apply
 def svd3(H):
     """(U, S, V, R, flipped) of a batch of 3x3 matrices (no autograd): the
     factors torch.svd would return plus the Kabsch rotation."""
-    H = H.contiguous().float()
-    b = H.shape[0]
-    R, U, V = torch.empty_like(H), torch.empty_like(H), torch.empty_like(H)
-    S = torch.empty(b, 3, device=H.device, dtype=torch.float32)
-    flipped = torch.empty(b, device=H.device, dtype=torch.int32)
-    call("mvp_kabsch_svd3", H.device, b, H, R, U, S, V, flipped)
-    return U, S, V, R, flipped
+    return _svd3_launch(H)
 
 
 # ---------------------------------------------------------------------------------------------------- DeepGMR
@@ -108,6 +111,18 @@ def svd3(H):
 
 def _on_op_layer(t):
     return t.is_cuda and t.dtype == torch.float32
+
+
+def _kernel_reads(tensors, aligned):
+    """Whether a kernel takes these tensors as they are: float32 CUDA, contiguous, all on one device, and those of `aligned`
+    on 16-byte addresses (the kernels load them four floats at a time)."""
+    return (all(_on_op_layer(t) and t.is_contiguous() and t.device == tensors[0].device for t in tensors)
+            and all(t.data_ptr() % 16 == 0 for t in aligned))
+
+
+def _scratch(nbytes, device):
+    """A kernel's (scratch, nbytes) argument pair: a fresh byte buffer, None where it asks for none."""
+    return (torch.empty(nbytes, device=device, dtype=torch.uint8) if nbytes else None), nbytes
 
 
 def _knn_reference(xyz, k):
@@ -260,12 +275,35 @@ def gmm_register(pi_s, mu_s, mu_t, sigma_t):
     return torch.cat([torch.cat([R, t], dim=2), bottom], dim=1)
 
 
+# ----------------------------------------------------------------------------------------------- DCP's switches
+# registration/models/dcp.py reads these where it chooses a route (DGCNN._route, LayerNorm.forward).  Plain module attributes,
+# all off: a route changes a summation order, and a default flips in a change of its own.
+
+EDGE_MLP = False           # True: DGCNN.forward takes the fused route in eval mode (float32 CUDA, nothing requires grad)
+LAYER_NORM = False         # True: LayerNorm.forward and the transformer's residual sums take ref_layer_norm
+EDGE_BN = False            # True: DGCNN.forward runs stages 1-4 through bn_relu_max when training or a gradient is needed
+
+
+@contextlib.contextmanager
+def routes(*, edge_mlp=None, layer_norm=None, edge_bn=None):
+    """Set the named switches (EDGE_MLP, LAYER_NORM, EDGE_BN) for the length of a `with` block: None leaves a switch as it is,
+    and every switch named gets back the value it had on the way in, also when the block raises.  Blocks nest.
+        with registration.routes(edge_mlp=True, layer_norm=True, edge_bn=True): ...
+    The switches are module attributes, so this is process-global and not thread-safe: every model in the process sees them,
+    and two threads inside blocks of their own restore each other's values."""
+    asked = {"EDGE_MLP": edge_mlp, "LAYER_NORM": layer_norm, "EDGE_BN": edge_bn}
+    module = globals()
+    before = {name: module[name] for name, on in asked.items() if on is not None}
+    module.update({name: bool(asked[name]) for name in before})
+    try:
+        yield
+    finally:
+        module.update(before)
+
+
 # ------------------------------------------------------------------------------------------- DGCNN's edge MLP (DCP)
 # registration/models/dcp.py: DGCNN in inference -- the neighbourhood gather, the 1x1 convolutions with BatchNorm's affine
 # map and ReLU, and the max over the k neighbours after each, as one kernel (mvp_edge_mlp_max, csrc/edge_mlp.hip).
-
-EDGE_MLP = False           # True: DGCNN.forward takes the fused route in eval mode (float32 CUDA, nothing requires grad)
-
 
 def _edge_mlp_reference(x, idx, weights, scales, shifts):
     """The composition mvp_edge_mlp_max computes, in torch: an explicit gather, then per stage the product with W_i, the
@@ -318,9 +356,6 @@ def edge_mlp_max(x, idx, weights, scales, shifts):
 # std -- and the residual addition in front of it, as one kernel each way (mvp_ref_layernorm[_backward],
 # csrc/layer_norm.hip).
 
-LAYER_NORM = False         # True: LayerNorm.forward and the transformer's residual sums take ref_layer_norm
-
-
 def _layer_norm_reference(z, a, b, eps):
     """The module's own formula, op for op (registration/models/dcp.py: LayerNorm.forward)."""
     centred = z - z.mean(-1, keepdim=True)
@@ -350,12 +385,8 @@ def _layer_norm_fits(x, a, b, residual):
     d = x.shape[-1] if x.dim() >= 1 else 0
     if not (d % 4 == 0 and 4 <= d <= 1024 and x.numel() < 2 ** 31 and a.shape == b.shape == (d,)):
         return False
-    tensors = (x, a, b) if residual is None else (x, a, b, residual)
-    if not all(_on_op_layer(t) and t.is_contiguous() and t.device == x.device for t in tensors):
-        return False
-    if x.data_ptr() % 16 != 0 or (residual is not None and residual.data_ptr() % 16 != 0):
-        return False
-    return residual is None or residual.shape == x.shape
+    rows = (x,) if residual is None else (x, residual)
+    return _kernel_reads(rows + (a, b), aligned=rows) and (residual is None or residual.shape == x.shape)
 
 
 def _aligned_rows(g):
@@ -398,8 +429,7 @@ class RefLayerNorm(Function):
             gz = torch.empty_like(z)
             ga = torch.empty_like(a) if need_a else None
             gb = torch.empty_like(a) if need_b else None
-            nbytes = ref_layernorm_backward_scratch_bytes(rows, d) if need_a or need_b else 0
-            scratch = torch.empty(nbytes, device=z.device, dtype=torch.uint8) if nbytes else None
+            scratch, nbytes = _scratch(ref_layernorm_backward_scratch_bytes(rows, d) if need_a or need_b else 0, z.device)
             if rows == 0:                                       # nothing is launched, nothing written
                 ga, gb = (None if ga is None else ga.zero_()), (None if gb is None else gb.zero_())
             call("mvp_ref_layernorm_backward", z.device, rows, d, z, a, gy, gres, stats, ctx.eps, gz, ga, gb, scratch, nbytes)
@@ -426,9 +456,6 @@ def ref_layer_norm(x, a, b, eps=1e-6, residual=None):
 # registration/models/dcp.py: DGCNN in training -- after each edge stage's 1x1 convolution, BatchNorm2d (batch or running
 # statistics), ReLU and the max over the k neighbours as kernels (mvp_edge_bn_stats, mvp_edge_bn_relu_max[_backward],
 # csrc/edge_bn.hip).  Saved for backward: z, two statistics per channel and one byte per pooled value; never r.
-
-EDGE_BN = False            # True: DGCNN.forward runs stages 1-4 through bn_relu_max when training or a gradient is needed
-
 
 def _bn_relu_max_reference(z, weight, bias, running_mean, running_var, training, momentum, eps, want_r=True):
     """The composition in torch: F.batch_norm, relu, max(dim=2).  momentum None leaves the running statistics alone (a
@@ -471,9 +498,7 @@ def _bn_relu_max_fits(z, weight, bias, running_mean, running_var, training, mome
     if training and b * k * n < 2:
         return False
     tensors = [z, weight, bias] + [t for t in running if t is not None]
-    if not all(_on_op_layer(t) and t.is_contiguous() and t.device == z.device for t in tensors):
-        return False
-    return z.data_ptr() % 16 == 0 and all(t.shape == (c,) for t in tensors[1:])
+    return _kernel_reads(tensors, aligned=(z,)) and all(t.shape == (c,) for t in tensors[1:])
 
 
 class BnReluMax(Function):
@@ -489,8 +514,7 @@ class BnReluMax(Function):
         if batch:
             stats = torch.empty(c, 2, device=z.device, dtype=torch.float32)
             var = torch.empty(c, device=z.device, dtype=torch.float32)
-            nbytes = edge_bn_scratch_bytes(b, c)
-            scratch = torch.empty(nbytes, device=z.device, dtype=torch.uint8)
+            scratch, nbytes = _scratch(edge_bn_scratch_bytes(b, c), z.device)
             call("mvp_edge_bn_stats", z.device, b, c, k, n, z, eps, stats, var, scratch, nbytes)
         r = torch.empty_like(z) if want_r else None
         pooled = torch.empty(b, c, n, device=z.device, dtype=torch.float32)
@@ -515,8 +539,7 @@ class BnReluMax(Function):
         ggamma = torch.empty_like(weight) if ctx.needs_input_grad[1] else None
         gbeta = torch.empty_like(bias) if ctx.needs_input_grad[2] else None
         sums = ctx.batch or ggamma is not None or gbeta is not None
-        nbytes = edge_bn_scratch_bytes(b, c) if sums else 0
-        scratch = torch.empty(nbytes, device=z.device, dtype=torch.uint8) if sums else None
+        scratch, nbytes = _scratch(edge_bn_scratch_bytes(b, c) if sums else 0, z.device)
         call("mvp_edge_bn_relu_max_backward", z.device, b, c, k, n, int(ctx.batch), z, stats, weight, bias, arg, g_r, g_pool,
              gz, ggamma, gbeta, scratch, nbytes)
         return (gz if ctx.needs_input_grad[0] else None), ggamma, gbeta, None, None, None

@@ -15,7 +15,8 @@ the 1x1 convolutions are library GEMMs -- except on DGCNN's opt-in inference rou
 maxima as one kernel and conv5 as one MFMA GEMM.  The transformer's LayerNorm and residual sums have an opt-in route of
 their own (mvp_benchmark_amd.registration.LAYER_NORM): every `x + f(...)` followed by a norm is one kernel, each way.
 DGCNN in training has a third (mvp_benchmark_amd.registration.EDGE_BN): BatchNorm, ReLU and the max over the neighbours of
-stages 1-4 as kernels, forward and backward.
+stages 1-4 as kernels, forward and backward.  Each module has ONE dataflow: the switches are read in two places, DGCNN._route
+and LayerNorm.forward (mvp_benchmark_amd.registration.routes sets them for a block).
 """
 import copy
 import math
@@ -64,12 +65,15 @@ class LayerNorm(nn.Module):
         self.eps = eps
 
     def forward(self, x, residual=None):
-        """norm(x); with a residual (only on the fused route): (x + residual, norm(x + residual)), one kernel."""
+        """The norm of z = x (+ residual): y, or (z, y) when a residual is given -- z is the residual stream's next value, so
+        `x = x + f(...); h = norm(x)` is one call, whatever the route.  The switch on: ref_layer_norm, one kernel for float32
+        CUDA tensors and this formula for every other; off: this formula, no kernel."""
         if _reg.LAYER_NORM:
             return _reg.ref_layer_norm(x, self.a_2, self.b_2, self.eps, residual)
-        assert residual is None
-        centred = x - x.mean(-1, keepdim=True)
-        return self.a_2 * centred / (x.std(-1, keepdim=True) + self.eps) + self.b_2
+        z = x if residual is None else x + residual
+        centred = z - z.mean(-1, keepdim=True)
+        y = self.a_2 * centred / (z.std(-1, keepdim=True) + self.eps) + self.b_2
+        return y if residual is None else (z, y)
 
 
 class SublayerConnection(nn.Module):
@@ -128,21 +132,13 @@ class TransformerLayer(nn.Module):
         self.sublayer = nn.ModuleList([SublayerConnection(size) for _ in range(2 if src_attn is None else 3)])
 
     def forward(self, x, memory=None):
-        if _reg.LAYER_NORM:
-            x, last = self.forward_deferred(x, memory)
-            return x + last
-        h = self.sublayer[0].norm(x)
-        x = x + self.self_attn(h, h)
-        branch = 1
-        if memory is not None:
-            x = x + self.src_attn(self.sublayer[1].norm(x), memory)
-            branch = 2
-        return x + self.feed_forward(self.sublayer[branch].norm(x))
+        x, last = self.branches(x, memory)
+        return x + last
 
-    def forward_deferred(self, x, memory=None, pending=None):
-        """The fused route (mvp_benchmark_amd.registration.LAYER_NORM): every branch's output is the `residual` of the NEXT
-        norm, which adds it to the stream and normalises the sum in one kernel.  `pending`: the previous layer's last branch,
-        not yet added to x.  -> (x, last): the layer's output is x + last, left to whoever normalises it next."""
+    def branches(self, x, memory=None, pending=None):
+        """The layer's one body: every branch's output is the `residual` of the NEXT norm, which adds it to the stream and
+        normalises the sum (one kernel on the fused route).  `pending`: the previous layer's last branch, not yet added to x.
+        -> (x, last): the layer's output is x + last, left to whoever normalises it next (LayerStack) or to forward."""
         norm = lambda i, x, branch: (x, self.sublayer[i].norm(x)) if branch is None else self.sublayer[i].norm(x, branch)
         x, h = norm(0, x, pending)
         branch = self.self_attn(h, h)
@@ -162,14 +158,10 @@ class LayerStack(nn.Module):
         self.norm = LayerNorm(layer.size)
 
     def forward(self, x, memory=None):
-        if _reg.LAYER_NORM:
-            pending = None                # a layer's last sum joins the next layer's first norm, or the final one
-            for layer in self.layers:
-                x, pending = layer.forward_deferred(x, memory, pending)
-            return self.norm(x) if pending is None else self.norm(x, pending)[1]
+        pending = None                    # a layer's last sum joins the next layer's first norm, or the final one
         for layer in self.layers:
-            x = layer(x, memory)
-        return self.norm(x)
+            x, pending = layer.branches(x, memory, pending)
+        return self.norm(x) if pending is None else self.norm(x, pending)[1]
 
 
 class EncoderDecoder(nn.Module):
@@ -206,15 +198,25 @@ class DGCNN(nn.Module):
     def _stage(self, i, x):
         return F.relu(getattr(self, "bn%d" % i)(getattr(self, "conv%d" % i)(x)))
 
-    def _fused(self, x):
-        """Whether forward(x) takes the fused inference route (mvp_benchmark_amd.registration.edge_mlp_max, then conv5 as
-        one MFMA GEMM): the switch is on, BatchNorm uses its running statistics, x is on the op layer (float32 CUDA, at most
-        4 channels, rows of whole 16-byte groups) and nothing asks for a gradient -- the route has no backward."""
-        if not _reg.EDGE_MLP or self.training or not (x.is_cuda and x.dtype == torch.float32):
-            return False
-        if x.dim() != 3 or x.size(1) > 4 or x.size(2) % 4 != 0:
-            return False
-        return not (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())))
+    def _route(self, x):
+        """forward(x)'s route, decided once and launching nothing: a pure function of the two switches, self.training, grad
+        mode and who requires grad, x's device, dtype and shape, and the BatchNorm configuration.
+          "edge_mlp"  stages 1-4 and their maxima as one kernel (mvp_benchmark_amd.registration.edge_mlp_max), then conv5 as one
+                      MFMA GEMM: EDGE_MLP is on, BatchNorm uses its running statistics (eval) and nothing asks for a gradient
+                      (the route has no backward); x has at most 4 channels and rows of whole 16-byte groups.
+          "edge_bn"   BatchNorm, ReLU and the max of stages 1-4 as kernels (mvp_benchmark_amd.registration.bn_relu_max): EDGE_BN
+                      is on, the module trains or some gradient is needed, and bn1..bn4 track their running statistics with a
+                      float momentum.
+          "composed"  everything else: both switches off, CPU, float64.
+        "edge_mlp" needs eval AND no gradient wanted, "edge_bn" training OR a gradient wanted: never both, whatever the switches."""
+        if not (_reg.EDGE_MLP or _reg.EDGE_BN) or x.dim() != 3 or not (x.is_cuda and x.dtype == torch.float32):
+            return "composed"
+        wanted = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+        if not (self.training or wanted):
+            return "edge_mlp" if _reg.EDGE_MLP and x.size(1) <= 4 and x.size(2) % 4 == 0 else "composed"
+        bns = [getattr(self, "bn%d" % i) for i in range(1, 5)]
+        tracked = all(bn.track_running_stats and bn.running_mean is not None and isinstance(bn.momentum, float) for bn in bns)
+        return "edge_bn" if _reg.EDGE_BN and tracked else "composed"
 
     def _forward_fused(self, x):
         """BatchNorm in eval mode is the per-channel map scale * t + shift; stages 1-4 and their maxima are one kernel, the
@@ -230,17 +232,6 @@ class DGCNN(nn.Module):
         w5 = self.conv5.weight.view(widths[4], -1) * scales[4].unsqueeze(1)
         return _pw.mfma_linear(pooled, w5.contiguous(), bias=shifts[4].contiguous(), relu=True)
 
-    def _edge_bn(self, x):
-        """Whether stages 1-4 run BatchNorm, ReLU and the max as kernels (mvp_benchmark_amd.registration.bn_relu_max): the
-        switch is on, x is float32 CUDA, the module trains or some gradient is needed (eval without gradients stays
-        composed, or EDGE_MLP's), and every BatchNorm tracks its running statistics with a float momentum."""
-        if not _reg.EDGE_BN or not (x.is_cuda and x.dtype == torch.float32) or x.dim() != 3:
-            return False
-        if not (self.training or (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())))):
-            return False
-        bns = [getattr(self, "bn%d" % i) for i in range(1, 5)]
-        return all(bn.track_running_stats and bn.running_mean is not None and isinstance(bn.momentum, float) for bn in bns)
-
     def _stage_edge_bn(self, i, edge, want_r):
         """conv_i, then BatchNorm + ReLU + max over k in one operator -> (relu(bn(conv(edge))) or None, its maximum (B,C,N));
         num_batches_tracked counts as nn.BatchNorm2d counts it."""
@@ -251,16 +242,16 @@ class DGCNN(nn.Module):
         return _reg.bn_relu_max(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.training, bn.momentum, bn.eps, want_r)
 
     def forward(self, x):
-        if self._fused(x):
+        route = self._route(x)
+        if route == "edge_mlp":
             return self._forward_fused(x.detach())
         batch_size, _, num_points = x.size()
         # (B, 6, 20, N): knn + grouping operators; neighbours on the SLOW spatial axis (the stages are
         # 1x1 convolutions + per-channel BatchNorm: layout-agnostic; the reference keeps (B, 6, N, 20))
         edge = get_graph_feature(x, k_major=True)
         pooled = []
-        fused_bn = self._edge_bn(x)
         for i in range(1, 5):
-            if fused_bn:                                              # stage 4's activations feed only their maximum
+            if route == "edge_bn":                                    # stage 4's activations feed only their maximum
                 edge, top = self._stage_edge_bn(i, edge, want_r=i < 4)
                 pooled.append(top.unsqueeze(2))
             else:

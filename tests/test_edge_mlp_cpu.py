@@ -3,14 +3,12 @@ binding, the switch, DGCNN's routing function, the torch composition of the wrap
 rounding bound of the GPU tests checked on the float32 torch composition (so the bound is one the reference formulation
 itself meets, with room, and is not vacuous)."""
 import ctypes
-import importlib.util
-import os
 
 import pytest
 import torch
-from conftest import ROOT
 
 import edge_mlp_cases as cases
+from dcp_util import OpLayerTensor, load_dcp
 
 OK, EBADSHAPE, EBADARG = 0, -1, -2
 
@@ -21,13 +19,6 @@ def _entry():
     null = ctypes.c_void_p(0)
     # (b, c, n, k, stages, w1..w4), x .. out, stream
     return lambda b, c, n, k, stages, *w, ptr=null: lib.mvp_edge_mlp_max(b, c, n, k, stages, *w, *([ptr] * 6), null)
-
-
-def _dcp():
-    spec = importlib.util.spec_from_file_location("registration_dcp_edge_mlp_cpu", os.path.join(ROOT, "registration", "models", "dcp.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 def test_shape_guards_and_null_buffers():
@@ -80,50 +71,36 @@ def test_switch_defaults_to_off():
     assert registration.EDGE_MLP is False
 
 
-class _OpLayerTensor:
-    """What DGCNN._fused reads of its input, for a float32 CUDA tensor that a machine without a GPU cannot make."""
-    is_cuda, dtype, requires_grad = True, torch.float32, False
-
-    def __init__(self, *shape):
-        self.shape = shape
-
-    def dim(self):
-        return len(self.shape)
-
-    def size(self, i):
-        return self.shape[i]
-
-
 def test_routing_function(monkeypatch):
-    dcp = _dcp()
+    dcp = load_dcp("edge_mlp_cpu")
     from mvp_benchmark_amd import registration
     net = dcp.DGCNN().eval()
-    x_gpu, x_cpu = _OpLayerTensor(2, 3, 64), torch.zeros(2, 3, 64)
+    x_gpu, x_cpu = OpLayerTensor(2, 3, 64), torch.zeros(2, 3, 64)
     with torch.no_grad():
-        assert net._fused(x_gpu) is False                        # the switch is off
+        assert net._route(x_gpu) == "composed"                        # the switch is off
     monkeypatch.setattr(registration, "EDGE_MLP", True)
     with torch.no_grad():
-        assert net._fused(x_gpu) is True
-        assert net._fused(x_cpu) is False                        # CPU
-        assert net.double()._fused(x_cpu.double()) is False      # float64
+        assert net._route(x_gpu) == "edge_mlp"
+        assert net._route(x_cpu) == "composed"                        # CPU
+        assert net.double()._route(x_cpu.double()) == "composed"      # float64
         net.float()
-        assert net._fused(_OpLayerTensor(2, 3, 66)) is False     # rows that are no whole 16-byte groups (conv5's GEMM)
-        assert net._fused(_OpLayerTensor(2, 5, 64)) is False     # more channels than the kernel gathers
+        assert net._route(OpLayerTensor(2, 3, 66)) == "composed"     # rows that are no whole 16-byte groups (conv5's GEMM)
+        assert net._route(OpLayerTensor(2, 5, 64)) == "composed"     # more channels than the kernel gathers
         net.train()
-        assert net._fused(x_gpu) is False                        # batch statistics
+        assert net._route(x_gpu) == "composed"                        # batch statistics
         net.eval()
-    assert net._fused(x_gpu) is False                            # grad mode and the parameters require grad
-    wants = _OpLayerTensor(2, 3, 64)
+    assert net._route(x_gpu) == "composed"                            # grad mode and the parameters require grad
+    wants = OpLayerTensor(2, 3, 64)
     wants.requires_grad = True
     for p in net.parameters():
         p.requires_grad_(False)
-    assert net._fused(x_gpu) is True and net._fused(wants) is False
+    assert net._route(x_gpu) == "edge_mlp" and net._route(wants) == "composed"
     with torch.no_grad():
-        assert net._fused(wants) is True
+        assert net._route(wants) == "edge_mlp"
 
 
 def test_cpu_and_float64_take_the_composed_route_whatever_the_switch(monkeypatch):
-    dcp = _dcp()
+    dcp = load_dcp("edge_mlp_cpu")
     from mvp_benchmark_amd import registration
     torch.manual_seed(3)
     net = dcp.DGCNN().double().eval()

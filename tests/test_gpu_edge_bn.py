@@ -6,9 +6,7 @@ Model level, measured on an MI355X (test_dgcnn_against_its_float64_copy prints t
 worst tensor's max |difference| / max |reference| on the golden clouds is 2.514e-06 on the fused route against 2.547e-06 on
 the composed one, on the random (2, 3, 68) input 1.398e-06 against 1.712e-06; the fused route's may be at most 4 times the
 composed route's.  The kernels use at most 0.42 of any bound of tests/edge_bn_cases.py."""
-import contextlib
 import copy
-import importlib.util
 import os
 import types
 
@@ -18,6 +16,7 @@ import torch
 from conftest import ROOT
 
 import edge_bn_cases as cases
+from dcp_util import abi_call_names, load_dcp, rel_err
 
 DEV = "cuda:0"
 gpu = pytest.mark.gpu
@@ -306,22 +305,6 @@ def test_ties_go_to_the_lowest_neighbour():
     within("ties batch", "gz", wb["gz"], back["gz"], back["mag_gz"], cases.T_GZ)
 
 
-@contextlib.contextmanager
-def abi_call_names():
-    """Names of the C-ABI entry points mvp_benchmark_amd.registration calls inside the block."""
-    import mvp_benchmark_amd.registration as R_
-    names, real = [], R_.call
-
-    def spy(name, *args):
-        names.append(name)
-        return real(name, *args)
-    R_.call = spy
-    try:
-        yield names
-    finally:
-        R_.call = real
-
-
 @gpu
 def test_refusals_and_the_composed_route():
     from mvp_benchmark_amd import _lib
@@ -366,27 +349,6 @@ def test_refusals_and_the_composed_route():
 
 # ---------------------------------------------------------------------------------------------- the module and the model
 
-def _dcp():
-    spec = importlib.util.spec_from_file_location("registration_dcp_edge_bn_gpu", os.path.join(ROOT, "registration", "models", "dcp.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-@contextlib.contextmanager
-def edge_bn_switch(on):
-    import mvp_benchmark_amd.registration as R_
-    old, R_.EDGE_BN = R_.EDGE_BN, on
-    try:
-        yield
-    finally:
-        R_.EDGE_BN = old
-
-
-def _rel_err(got, want):
-    return float((got.detach().cpu().double() - want).abs().max()) / float(want.abs().max())
-
-
 @gpu
 @pytest.mark.parametrize("which", ["golden", "random68"])
 def test_dgcnn_against_its_float64_copy(which):
@@ -395,7 +357,8 @@ def test_dgcnn_against_its_float64_copy(which):
     rounding error of these stages).  A tensor's error = max |difference| / max |reference|, over the output, the input's
     gradient, every parameter gradient and every running statistic; a ROUTE's error is its worst tensor's.  The fused route's
     may be at most 4 times the composed route's: both carry the convolutions' rounding, which dominates."""
-    dcp = _dcp()
+    from mvp_benchmark_amd.registration import routes
+    dcp = load_dcp("edge_bn_gpu")
     torch.manual_seed(31)
     net = dcp.DGCNN().train()
     with torch.no_grad():                                       # BatchNorms away from gamma = 1, beta = 0
@@ -430,13 +393,13 @@ def test_dgcnn_against_its_float64_copy(which):
     errs = {}
     for on in (True, False):
         netd = copy.deepcopy(net).to(DEV)
-        with edge_bn_switch(on), abi_call_names() as names:
+        with routes(edge_bn=on), abi_call_names() as names:
             got, count = run(netd, x.to(DEV), w.float().to(DEV))
         assert names.count("mvp_edge_bn_stats") == (4 if on else 0), names
         assert names.count("mvp_edge_bn_relu_max") == names.count("mvp_edge_bn_relu_max_backward") == (4 if on else 0), names
         assert count == want_count and all(v == 1 for v in count.values()) and len(count) == 5
         assert got.keys() == want.keys() and all(bool(torch.isfinite(v).all()) for v in got.values())
-        errs[on] = {k: _rel_err(got[k], want[k]) for k in want}
+        errs[on] = {k: rel_err(got[k], want[k]) for k in want}
     for k in errs[True]:
         print("DGCNN %s %-28s fused %.3e composed %.3e" % (which, k, errs[True][k], errs[False][k]))
     worst = {on: max(errs[on].values()) for on in (True, False)}
@@ -449,7 +412,8 @@ def test_dgcnn_against_its_float64_copy(which):
 def test_dcp_training_step_on_the_fused_route():
     """One Model training step with T_gt and the switch on: a finite loss, a gradient on every parameter, the module tree of
     the switched-off model (and the golden fixture's parameter names), num_batches_tracked counted once per cloud."""
-    dcp = _dcp()
+    from mvp_benchmark_amd.registration import routes
+    dcp = load_dcp("edge_bn_gpu")
     g = np.load(os.path.join(GOLD, "dcp_golden.npz"))
     torch.manual_seed(34)
     net = dcp.Model(types.SimpleNamespace())
@@ -457,7 +421,7 @@ def test_dcp_training_step_on_the_fused_route():
     assert set(str(n) for n in g["names"]) <= set(keys)
     net = net.train().to(DEV)
     src, tgt, T_gt = (torch.tensor(g[k], device=DEV) for k in ("src", "tgt", "T_gt"))
-    with edge_bn_switch(True), abi_call_names() as names:
+    with routes(edge_bn=True), abi_call_names() as names:
         loss = net(src, tgt, T_gt)[0].mean()
         loss.backward()
     assert names.count("mvp_edge_bn_stats") == 8 and names.count("mvp_edge_bn_relu_max_backward") == 8, names
@@ -469,7 +433,7 @@ def test_dcp_training_step_on_the_fused_route():
     assert all(int(getattr(net.emb_nn, "bn%d" % i).num_batches_tracked) == 2 for i in range(1, 6))
     # eval without gradients stays on the composed route
     net.eval()
-    with edge_bn_switch(True), abi_call_names() as names, torch.no_grad():
+    with routes(edge_bn=True), abi_call_names() as names, torch.no_grad():
         net(src, tgt)
     assert not any(n.startswith("mvp_edge_bn") for n in names), names
     import mvp_benchmark_amd.registration as R_

@@ -12,9 +12,7 @@ Two kinds of input, two kinds of assertion, no tuned tolerance:
   random   randn inputs, weights scaled by 1 / sqrt(K): |got - ref| <= t * 2^-24 * mag elementwise.
 
 Indices always lie in [0, N)."""
-import contextlib
 import copy
-import importlib.util
 import os
 import sys
 import types
@@ -25,6 +23,7 @@ import torch
 from conftest import ROOT
 
 import edge_mlp_cases as cases
+from dcp_util import abi_call_names, load_dcp
 
 DEV = "cuda:0"
 gpu = pytest.mark.gpu
@@ -119,44 +118,6 @@ def test_two_runs_give_the_same_bits():
 
 # ---------------------------------------------------------------------------------------------- the module and the model
 
-def _dcp():
-    spec = importlib.util.spec_from_file_location("registration_dcp_edge_mlp_gpu", os.path.join(ROOT, "registration", "models", "dcp.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-@contextlib.contextmanager
-def abi_call_names():
-    """Names of the C-ABI entry points the op layer calls inside the block."""
-    import mvp_benchmark_amd.mm3d_pn2.functional as F_
-    import mvp_benchmark_amd.pointwise as P_
-    import mvp_benchmark_amd.registration as R_
-    names, real = [], R_.call
-
-    def spy(name, *args):
-        names.append(name)
-        return real(name, *args)
-    saved = [(m, m.call) for m in (F_, P_, R_)]
-    for m, _ in saved:
-        m.call = spy
-    try:
-        yield names
-    finally:
-        for m, fn in saved:
-            m.call = fn
-
-
-@contextlib.contextmanager
-def edge_mlp_switch(on):
-    import mvp_benchmark_amd.registration as R_
-    old, R_.EDGE_MLP = R_.EDGE_MLP, on
-    try:
-        yield
-    finally:
-        R_.EDGE_MLP = old
-
-
 def _randomised_dgcnn(dcp):
     """A DGCNN whose BatchNorm layers carry random running statistics and affine parameters, some weights negative."""
     torch.manual_seed(11)
@@ -207,7 +168,8 @@ def test_dgcnn_module_against_its_float64_copy(which, monkeypatch):
     against a float64 CPU copy of the module on the same neighbour graph (taken from the float64 copy's knn and injected,
     so the test is about the op, not about kNN ties).  The fused route must stay within the rounding bound
     (_module_reference counts the roundings of scale and shift); both routes' largest errors are printed (-s)."""
-    dcp = _dcp()
+    from mvp_benchmark_amd.registration import routes
+    dcp = load_dcp("edge_mlp_gpu")
     net = _randomised_dgcnn(dcp)
     x = _golden_clouds() if which == "golden" else torch.randn(2, 3, 300, generator=torch.Generator().manual_seed(13))
     net64 = copy.deepcopy(net).double()
@@ -220,7 +182,7 @@ def test_dgcnn_module_against_its_float64_copy(which, monkeypatch):
     netd, xd = copy.deepcopy(net).to(DEV), x.to(DEV)
     outs = {}
     for on in (True, False):
-        with edge_mlp_switch(on), abi_call_names() as names, torch.no_grad():
+        with routes(edge_mlp=on), abi_call_names() as names, torch.no_grad():
             outs[on] = netd(xd).cpu()
         assert ("mvp_edge_mlp_max" in names) == on and ("mvp_group_points" in names) == (not on), names
         if on:
@@ -235,7 +197,7 @@ def test_dgcnn_module_against_its_float64_copy(which, monkeypatch):
     trained = {}
     for on in (True, False):
         nett = copy.deepcopy(net).to(DEV).train()
-        with edge_mlp_switch(on), abi_call_names() as names, torch.no_grad():
+        with routes(edge_mlp=on), abi_call_names() as names, torch.no_grad():
             trained[on] = nett(xd).cpu()
         assert "mvp_edge_mlp_max" not in names and "mvp_group_points" in names
     assert torch.equal(trained[True], trained[False])
@@ -248,13 +210,14 @@ def test_dcp_model_matches_the_reference_fixture_on_the_fused_route():
     if GOLD not in sys.path:
         sys.path.insert(0, GOLD)
     from make_dcp_golden import fill_parameters
-    dcp = _dcp()
+    from mvp_benchmark_amd.registration import routes
+    dcp = load_dcp("edge_mlp_gpu")
     g = np.load(os.path.join(GOLD, "dcp_golden.npz"))
     net = dcp.Model(types.SimpleNamespace())
     fill_parameters(net)
     net = net.eval().to(DEV)
     src, tgt, T_gt = (torch.tensor(g[k], device=DEV) for k in ("src", "tgt", "T_gt"))
-    with edge_mlp_switch(True), abi_call_names() as names, torch.no_grad():
+    with routes(edge_mlp=True), abi_call_names() as names, torch.no_grad():
         T_12 = net(src, tgt)
         loss, r_err, t_err, rmse, rt_mse = net(src, tgt, T_gt)
     assert names.count("mvp_edge_mlp_max") == 4 and "mvp_group_points" not in names

@@ -1,9 +1,7 @@
 """The fused LayerNorm + residual sum (csrc/layer_norm.hip, registration.ref_layer_norm, the transformer's opt-in route) against
 the float64 reference and the bounds of tests/layer_norm_cases.py.  Every shape runs through the C ABI on NaN-filled
 outputs (an element no lane writes stays NaN) and through the wrapper."""
-import contextlib
 import copy
-import importlib.util
 import os
 import sys
 import types
@@ -14,6 +12,7 @@ import torch
 from conftest import ROOT
 
 import layer_norm_cases as cases
+from dcp_util import abi_call_names, load_dcp, rel_err
 
 DEV = "cuda:0"
 gpu = pytest.mark.gpu
@@ -272,43 +271,6 @@ def test_refusals():
 
 # ---------------------------------------------------------------------------------------------- the module and the model
 
-def _dcp():
-    spec = importlib.util.spec_from_file_location("registration_dcp_layer_norm_gpu", os.path.join(ROOT, "registration", "models", "dcp.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-@contextlib.contextmanager
-def layer_norm_switch(on):
-    import mvp_benchmark_amd.registration as R_
-    old, R_.LAYER_NORM = R_.LAYER_NORM, on
-    try:
-        yield
-    finally:
-        R_.LAYER_NORM = old
-
-
-@contextlib.contextmanager
-def abi_call_names():
-    """Names of the C-ABI entry points mvp_benchmark_amd.registration calls inside the block."""
-    import mvp_benchmark_amd.registration as R_
-    names, real = [], R_.call
-
-    def spy(name, *args):
-        names.append(name)
-        return real(name, *args)
-    R_.call = spy
-    try:
-        yield names
-    finally:
-        R_.call = real
-
-
-def _rel_err(got, want):
-    return float((got.detach().cpu().double() - want).abs().max()) / float(want.abs().max())
-
-
 def _transformer_inputs(dcp, which):
     if which == "golden":                                       # the golden clouds' embeddings, (2, 512, 64) each
         g = np.load(os.path.join(GOLD, "dcp_golden.npz"))
@@ -333,7 +295,8 @@ def test_transformer_module_against_its_float64_copy(which):
     2.0e-6).  The four key projections' biases have no relative error: softmax does not see a shift common to all keys, their
     gradient is 0 in exact arithmetic (1e-16 of their weights' in float64), what float32 leaves there is noise on both
     routes; they are held to 1e-4 of their weight gradient's largest entry instead (noise of u sqrt(rows) size is 1e-6)."""
-    dcp = _dcp()
+    from mvp_benchmark_amd.registration import routes
+    dcp = load_dcp("layer_norm_gpu")
     torch.manual_seed(23)
     net = dcp.Transformer(types.SimpleNamespace())
     with torch.no_grad():                                       # norms away from a = 1, b = 0
@@ -357,7 +320,7 @@ def test_transformer_module_against_its_float64_copy(which):
     netd = copy.deepcopy(net).to(DEV)
     errs = {}
     for on in (True, False):
-        with layer_norm_switch(on), abi_call_names() as names:
+        with routes(layer_norm=on), abi_call_names() as names:
             outs, grads = run(netd, src.to(DEV), tgt.to(DEV), w_src.float().to(DEV), w_tgt.float().to(DEV))
         # 2 * (3 + 4) norms each way when on, none when off
         assert names.count("mvp_ref_layernorm") == (14 if on else 0), names
@@ -368,8 +331,8 @@ def test_transformer_module_against_its_float64_copy(which):
         for k in zero:                                          # 0 in exact arithmetic
             scale = float(want_grad[k.replace("bias", "weight")].abs().max())
             assert float(want_grad[k].abs().max()) <= 1e-12 * scale and float(grads[k].abs().max()) <= 1e-4 * scale, k
-        errs[on] = {"out%d" % i: _rel_err(o, w) for i, (o, w) in enumerate(zip(outs, want_out))}
-        errs[on].update({k: _rel_err(grads[k], want_grad[k]) for k in want_grad if k not in zero})
+        errs[on] = {"out%d" % i: rel_err(o, w) for i, (o, w) in enumerate(zip(outs, want_out))}
+        errs[on].update({k: rel_err(grads[k], want_grad[k]) for k in want_grad if k not in zero})
     for k in errs[True]:
         print("Transformer %s %-55s fused %.3e composed %.3e" % (which, k, errs[True][k], errs[False][k]))
     route = {on: (max(v for k, v in errs[on].items() if k.startswith("out")),
@@ -386,14 +349,15 @@ def test_dcp_model_on_the_fused_route():
     if GOLD not in sys.path:
         sys.path.insert(0, GOLD)
     from make_dcp_golden import fill_parameters
-    dcp = _dcp()
+    from mvp_benchmark_amd.registration import routes
+    dcp = load_dcp("layer_norm_gpu")
     g = np.load(os.path.join(GOLD, "dcp_golden.npz"))
     net = dcp.Model(types.SimpleNamespace())
     fill_parameters(net)
     keys = list(net.state_dict())
     net = net.eval().to(DEV)
     src, tgt, T_gt = (torch.tensor(g[k], device=DEV) for k in ("src", "tgt", "T_gt"))
-    with layer_norm_switch(True), abi_call_names() as names, torch.no_grad():
+    with routes(layer_norm=True), abi_call_names() as names, torch.no_grad():
         T_12 = net(src, tgt)
         loss, r_err, t_err, rmse, rt_mse = net(src, tgt, T_gt)
     assert names.count("mvp_ref_layernorm") == 28 and "mvp_ref_layernorm_backward" not in names
@@ -404,7 +368,7 @@ def test_dcp_model_on_the_fused_route():
     np.testing.assert_allclose(rmse.cpu().numpy(), g["rmse"], rtol=1e-3, atol=2e-4)
     np.testing.assert_allclose(rt_mse.cpu().numpy(), g["rt_mse"], rtol=1e-3, atol=5e-4)
     net.train()
-    with layer_norm_switch(True), abi_call_names() as names:
+    with routes(layer_norm=True), abi_call_names() as names:
         net(src, tgt, T_gt)[0].mean().backward()
     assert names.count("mvp_ref_layernorm") == 14 and names.count("mvp_ref_layernorm_backward") == 14
     grads = {k: p.grad for k, p in net.named_parameters() if p.requires_grad}

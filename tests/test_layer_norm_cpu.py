@@ -4,24 +4,15 @@ bounds of tests/layer_norm_cases.py checked on the float32 torch composition (me
 (missed by far), so the GPU tests' bound is neither vacuous nor out of reach."""
 import copy
 import ctypes
-import importlib.util
-import os
 import types
 
 import pytest
 import torch
-from conftest import ROOT
 
 import layer_norm_cases as cases
+from dcp_util import load_dcp
 
 OK, EBADSHAPE, EBADARG = 0, -1, -2
-
-
-def _dcp():
-    spec = importlib.util.spec_from_file_location("registration_dcp_layer_norm_cpu", os.path.join(ROOT, "registration", "models", "dcp.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 def _inputs(rows, d, seed=0, dtype=torch.float64, shape=None):
@@ -47,7 +38,7 @@ def test_switch_defaults_to_off():
 @pytest.mark.parametrize("with_residual", [False, True])
 def test_wrapper_on_float64_cpu_equals_the_composed_module(with_residual):
     from mvp_benchmark_amd.registration import ref_layer_norm
-    dcp = _dcp()
+    dcp = load_dcp("layer_norm_cpu")
     x, a, b, res = _inputs(5, 60, shape=(2, 5))
     norm = dcp.LayerNorm(60).double()
     with torch.no_grad():
@@ -115,7 +106,7 @@ def test_closed_form_backward_on_a_constant_row(d):
 
 def test_cpu_model_with_the_switch_on_equals_the_switch_off(monkeypatch):
     """The fused route is float32 CUDA only: on the CPU the switch re-orders nothing, outputs and gradients are the same bits."""
-    dcp = _dcp()
+    dcp = load_dcp("layer_norm_cpu")
     from mvp_benchmark_amd import registration
     torch.manual_seed(6)
     proto = dcp.Model(types.SimpleNamespace()).train()

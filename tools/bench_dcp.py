@@ -15,7 +15,12 @@ import torch
 import dcp
 import train_utils as tu
 
+import mvp_benchmark_amd.registration as reg_ops
+from mvp_benchmark_amd import _lib
+
 REPS = int(os.environ.get("MVP_BENCH_REPS", "10"))
+ROUNDS = max(5, int(os.environ.get("MVP_BENCH_AB_ROUNDS", "5")))
+HBM_SPEC, HBM_COPY = 8.0, 6.29                           # TB/s: MI355X spec, measured float4 copy
 dev = "cuda:0"
 B, N = 128, 1024
 torch.manual_seed(0)
@@ -36,6 +41,54 @@ def timed(fn, reps=REPS):
         fn()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / reps * 1e3
+
+
+def alternate(switch, cases, width, tail):
+    """The A/B of one switch of mvp_benchmark_amd.registration (`switch`: routes()' keyword for it), every other switch off: per
+    case (name, fn, training, after) ROUNDS alternations of composed / fused, REPS repetitions each, one printed line -- the
+    medians with [min .. max], then `tail` filled from ratio, diff and faster -- and after(med), where given, for a line of
+    the case's own.  -> {name: fused faster than composed in every alternation}."""
+    faster = {}
+    for name, fn, training, after in cases:
+        net.train(training)
+        ms = {False: [], True: []}
+        for _ in range(ROUNDS):
+            for on in (False, True):
+                with reg_ops.routes(**{switch: on}):
+                    ms[on].append(timed(fn))
+        med = {on: sorted(v)[len(v) // 2] for on, v in ms.items()}
+        faster[name] = all(f < c for f, c in zip(ms[True], ms[False]))
+        print("  %-*s composed %7.2f [%7.2f .. %7.2f]   fused %7.2f [%7.2f .. %7.2f]   " % (
+            width, name, med[False], min(ms[False]), max(ms[False]), med[True], min(ms[True]), max(ms[True])) + tail % {
+                "ratio": med[False] / med[True], "diff": med[False] - med[True], "faster": "yes" if faster[name] else "NO"},
+            flush=True)
+        if after is not None:
+            after(med)
+    return faster
+
+
+def peak_memory(switch):
+    """The training step's torch.cuda.max_memory_allocated per route of one switch, in GB -> {on: GB}."""
+    net.train()
+    peak = {}
+    for on in (False, True):
+        with reg_ops.routes(**{switch: on}):
+            fwd_bwd(); torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            fwd_bwd(); torch.cuda.synchronize()
+            peak[on] = torch.cuda.max_memory_allocated() / 1e9
+        print("  training step, %s route: torch.cuda.max_memory_allocated %.2f GB" % ("fused" if on else "composed", peak[on]), flush=True)
+    return peak
+
+
+def kernels_alone(entries, tensor_bytes, reps, lead):
+    """Entry points on their own: per (name, passes over a tensor of tensor_bytes, fn) the median of five timings of `reps`
+    calls and the bytes/s of the algorithmic bytes beside the HBM rates; `lead` formats the name."""
+    for name, passes, fn in entries:
+        t = sorted(timed(fn, reps) for _ in range(5))[2]
+        rate = passes * tensor_bytes / t / 1e9                                  # TB/s: bytes / ms / 1e9
+        print(lead % name + " %7.3f ms  %5.2f TB/s = %4.1f %% of spec, %4.1f %% of the copy rate" % (
+            t, rate, rate / HBM_SPEC * 100, rate / HBM_COPY * 100), flush=True)
 
 
 def fwd():
@@ -82,8 +135,6 @@ for name, fn in (("forward", fwd), ("forward + backward", fwd_bwd)):
 # ---- the fused edge MLP of DGCNN (mvp_benchmark_amd.registration.EDGE_MLP, default off): the two routes in this one process,
 # alternated (MVP_BENCH_AB_ROUNDS alternations, REPS repetitions each): the eval forward, emb_nn alone on both clouds, and
 # the edge stages alone (mvp_edge_mlp_max against the composed gather / conv / BatchNorm / ReLU / max chain).
-import mvp_benchmark_amd.registration as reg_ops
-ROUNDS = max(5, int(os.environ.get("MVP_BENCH_AB_ROUNDS", "5")))
 K_GRAPH, MAC_PER_COLUMN, PEAK = 20, 45440, 157.3         # 6*64 + 64*64 + 64*128 + 128*256 multiply-adds per edge; f32 MFMA TFLOP/s
 columns = 2 * B * N * K_GRAPH
 tflop = 2.0 * MAC_PER_COLUMN * columns / 1e12
@@ -120,32 +171,20 @@ print("# fused edge MLP A/B: %s; torch %s; %d alternations x %d repetitions, med
       "edge stages = %d MAC x %.2f M columns = %.0f GFLOP, float32 MFMA peak %.1f TFLOP/s" % (
           torch.cuda.get_device_name(0), torch.__version__, ROUNDS, REPS, MAC_PER_COLUMN, columns / 1e6, tflop * 1e3, PEAK),
       flush=True)
-for name, fn in (("eval forward", fwd), ("emb_nn (kNN + edge stages + conv5), both clouds", emb_both),
-                 ("edge stages alone, both clouds", edge_stages)):
-    ms = {False: [], True: []}
-    for _ in range(ROUNDS):
-        for on in (False, True):
-            reg_ops.EDGE_MLP = on
-            try:
-                ms[on].append(timed(fn))
-            finally:
-                reg_ops.EDGE_MLP = False
-    med = {on: sorted(v)[len(v) // 2] for on, v in ms.items()}
-    print("  %-48s composed %7.2f [%7.2f .. %7.2f]   fused %7.2f [%7.2f .. %7.2f]   composed / fused %.2f" % (
-        name, med[False], min(ms[False]), max(ms[False]), med[True], min(ms[True]), max(ms[True]), med[False] / med[True]),
-        flush=True)
-    if fn is not fwd:
-        print("  %-48s composed %6.1f TFLOP/s (%4.1f %% of peak)   fused %6.1f TFLOP/s (%4.1f %% of peak)%s" % (
-            "  the edge stages' arithmetic over that time:", tflop / med[False] * 1e3, tflop / med[False] * 1e5 / PEAK,
-            tflop / med[True] * 1e3, tflop / med[True] * 1e5 / PEAK,
-            "" if fn is edge_stages else "   (kNN and conv5 inside the time)"), flush=True)
+def arithmetic(note):
+    return lambda med: print("  %-48s composed %6.1f TFLOP/s (%4.1f %% of peak)   fused %6.1f TFLOP/s (%4.1f %% of peak)%s" % (
+        "  the edge stages' arithmetic over that time:", tflop / med[False] * 1e3, tflop / med[False] * 1e5 / PEAK,
+        tflop / med[True] * 1e3, tflop / med[True] * 1e5 / PEAK, note), flush=True)
+
+
+alternate("edge_mlp", (("eval forward", fwd, False, None),
+                       ("emb_nn (kNN + edge stages + conv5), both clouds", emb_both, False, arithmetic("   (kNN and conv5 inside the time)")),
+                       ("edge stages alone, both clouds", edge_stages, False, arithmetic(""))),
+          48, "composed / fused %(ratio).2f")
 
 # ---- the transformer's LayerNorm + residual sums as kernels (mvp_benchmark_amd.registration.LAYER_NORM, default off): the two
 # routes in this one process, alternated like the block above: the eval forward, the training step (forward + backward), the
 # transformer alone both ways; the training step's peak memory per route; then the two kernels alone at cfg 5's row count.
-from mvp_benchmark_amd import _lib
-
-
 def pointer_eval():
     with torch.no_grad():
         return net.pointer(f_src, f_tgt)
@@ -162,40 +201,16 @@ with torch.no_grad():
     f_src, f_tgt = net.emb_nn(clouds[0]), net.emb_nn(clouds[1])
 print("# fused LayerNorm + residual A/B: %d alternations x %d repetitions, median ms [min .. max]; 14 norms and 10 residual "
       "sums per forward over (%d, %d) rows" % (ROUNDS, REPS, B * N, dcp.EMB_DIMS), flush=True)
-faster = {}
-for name, fn, training in (("eval forward", fwd, False), ("forward + backward", fwd_bwd, True),
-                           ("transformer alone, eval forward", pointer_eval, False),
-                           ("transformer alone, forward + backward", pointer_train, True)):
-    (net.train() if training else net.eval())
-    ms = {False: [], True: []}
-    for _ in range(ROUNDS):
-        for on in (False, True):
-            reg_ops.LAYER_NORM = on
-            try:
-                ms[on].append(timed(fn))
-            finally:
-                reg_ops.LAYER_NORM = False
-    med = {on: sorted(v)[len(v) // 2] for on, v in ms.items()}
-    faster[name] = all(f < c for f, c in zip(ms[True], ms[False]))
-    print("  %-40s composed %7.2f [%7.2f .. %7.2f]   fused %7.2f [%7.2f .. %7.2f]   composed / fused %.3f   fused faster in "
-          "every alternation: %s" % (name, med[False], min(ms[False]), max(ms[False]), med[True], min(ms[True]),
-                                     max(ms[True]), med[False] / med[True], "yes" if faster[name] else "NO"), flush=True)
+faster = alternate("layer_norm", (("eval forward", fwd, False, None), ("forward + backward", fwd_bwd, True, None),
+                                  ("transformer alone, eval forward", pointer_eval, False, None),
+                                  ("transformer alone, forward + backward", pointer_train, True, None)),
+                   40, "composed / fused %(ratio).3f   fused faster in every alternation: %(faster)s")
 print("  criterion (fused faster than composed in every alternation, eval forward and forward + backward): %s" % (
     "met" if faster["eval forward"] and faster["forward + backward"] else "NOT met -- the switch stays off either way"), flush=True)
-net.train()
-for on in (False, True):
-    reg_ops.LAYER_NORM = on
-    try:
-        fwd_bwd(); torch.cuda.synchronize()
-        torch.cuda.reset_peak_memory_stats()
-        fwd_bwd(); torch.cuda.synchronize()
-        print("  training step, %s route: torch.cuda.max_memory_allocated %.2f GB" % (
-            "fused" if on else "composed", torch.cuda.max_memory_allocated() / 1e9), flush=True)
-    finally:
-        reg_ops.LAYER_NORM = False
+peak_memory("layer_norm")
 net.zero_grad(set_to_none=True)
 
-ROWS_LN, D_LN, HBM_SPEC, HBM_COPY = B * N, dcp.EMB_DIMS, 8.0, 6.29       # TB/s: MI355X spec, measured float4 copy
+ROWS_LN, D_LN = B * N, dcp.EMB_DIMS
 gl = torch.Generator().manual_seed(6)
 xs, ds_, gys, grs = ((torch.randn(ROWS_LN, D_LN, generator=gl) + 0.5).to(dev) for _ in range(4))
 al, bl = torch.randn(D_LN, generator=gl).to(dev), torch.randn(D_LN, generator=gl).to(dev)
@@ -219,11 +234,7 @@ kernels = (
 )
 print("# the kernels alone at (%d, %d) float32, %.0f MB a tensor; bytes/s from the algorithmic bytes; HBM %.1f TB/s spec, "
       "%.2f TB/s measured float4 copy" % (ROWS_LN, D_LN, tensor_bytes / 1e6, HBM_SPEC, HBM_COPY), flush=True)
-for name, passes, fn in kernels:
-    t = sorted(timed(fn, 20) for _ in range(5))[2]
-    rate = passes * tensor_bytes / t / 1e9                                  # TB/s: bytes / ms / 1e9
-    print("  %-70s %7.3f ms  %5.2f TB/s = %4.1f %% of spec, %4.1f %% of the copy rate" % (
-        name, t, rate, rate / HBM_SPEC * 100, rate / HBM_COPY * 100), flush=True)
+kernels_alone(kernels, tensor_bytes, 20, "  %-70s")
 
 # ---- DGCNN's BatchNorm + ReLU + max over k as kernels in training (mvp_benchmark_amd.registration.EDGE_BN, default off): the
 # two routes in this one process, alternated like the blocks above, every other switch off: emb_nn forward + backward on both
@@ -241,33 +252,9 @@ def emb_train():
 net.train()
 print("# fused BatchNorm + ReLU + max A/B (training): %d alternations x %d repetitions, median ms [min .. max]; 4 stages x 2 "
       "clouds over (%d, C, %d, %d), C = 64, 64, 128, 256" % (ROUNDS, REPS, B, K_GRAPH, N), flush=True)
-faster = {}
-for name, fn in (("emb_nn forward + backward, both clouds", emb_train), ("forward + backward", fwd_bwd)):
-    ms = {False: [], True: []}
-    for _ in range(ROUNDS):
-        for on in (False, True):
-            reg_ops.EDGE_BN = on
-            try:
-                ms[on].append(timed(fn))
-            finally:
-                reg_ops.EDGE_BN = False
-    med = {on: sorted(v)[len(v) // 2] for on, v in ms.items()}
-    faster[name] = all(f < c for f, c in zip(ms[True], ms[False]))
-    print("  %-40s composed %7.2f [%7.2f .. %7.2f]   fused %7.2f [%7.2f .. %7.2f]   composed - fused %6.2f ms   composed / "
-          "fused %.3f   fused faster in every alternation: %s" % (
-              name, med[False], min(ms[False]), max(ms[False]), med[True], min(ms[True]), max(ms[True]),
-              med[False] - med[True], med[False] / med[True], "yes" if faster[name] else "NO"), flush=True)
-peak = {}
-for on in (False, True):
-    reg_ops.EDGE_BN = on
-    try:
-        fwd_bwd(); torch.cuda.synchronize()
-        torch.cuda.reset_peak_memory_stats()
-        fwd_bwd(); torch.cuda.synchronize()
-        peak[on] = torch.cuda.max_memory_allocated() / 1e9
-        print("  training step, %s route: torch.cuda.max_memory_allocated %.2f GB" % ("fused" if on else "composed", peak[on]), flush=True)
-    finally:
-        reg_ops.EDGE_BN = False
+faster = alternate("edge_bn", (("emb_nn forward + backward, both clouds", emb_train, True, None), ("forward + backward", fwd_bwd, True, None)),
+                   40, "composed - fused %(diff)6.2f ms   composed / fused %(ratio).3f   fused faster in every alternation: %(faster)s")
+peak = peak_memory("edge_bn")
 print("  criterion (fused faster than composed in every alternation of forward + backward, and a lower peak): %s" % (
     "met" if faster["forward + backward"] and peak[True] < peak[False] else "NOT met -- the switch stays off either way"), flush=True)
 net.zero_grad(set_to_none=True)
@@ -303,10 +290,6 @@ for C, which in ((64, "stages 1 and 2"), (128, "stage 3"), (256, "stage 4")):
          lambda: _lib.call("mvp_edge_bn_relu_max_backward", dev, *dims, 1, ze, ste, gam, bet, ae, None, gpe, gze, gga, gbe, sce, nbe)),
     )
     print("  C = %d (%s), T = %.0f MB" % (C, which, T / 1e6), flush=True)
-    for name, passes, fn in entries:
-        t = sorted(timed(fn, 10) for _ in range(5))[2]
-        rate = passes * T / t / 1e9
-        print("    %-74s %7.3f ms  %5.2f TB/s = %4.1f %% of spec, %4.1f %% of the copy rate" % (
-            name, t, rate, rate / HBM_SPEC * 100, rate / HBM_COPY * 100), flush=True)
+    kernels_alone(entries, T, 10, "    %-74s")
     del ze, gre, gpe, re_, gze
     torch.cuda.empty_cache()
