@@ -71,8 +71,30 @@ SIGNATURES = {
     "mvp_edge_bn_relu_max": "iiiippppppp",
     "mvp_edge_bn_relu_max_backward": "iiiiipppppppppppq",
 }
+# The host-only entry points (no stream, nothing launched): name -> (return kind, argument kinds); s = const char *.
+# With SIGNATURES this is every prototype of include/mvpops.h (tests/test_host.py checks both against the header).
+HOST_SIGNATURES = {
+    "mvp_abi_version": ("i", ""),
+    "mvp_last_hip_error": ("s", ""),
+    "mvp_emd_scratch_bytes": ("q", "ii"),
+    "mvp_emd_configure": ("i", "iiii"),
+    "mvp_chamfer_scratch_bytes": ("q", "iii"),
+    "mvp_knn_scratch_bytes": ("q", "iii"),
+    "mvp_fps_scratch_bytes": ("q", "ii"),
+    "mvp_fps_cluster_scratch_bytes": ("q", "i"),
+    "mvp_scatter_scratch_bytes": ("q", "iiii"),
+    "mvp_pointwise_wgrad_scratch_bytes": ("q", "iiii"),
+    "mvp_pointwise_wgrad_mfma_scratch_bytes": ("q", "iiiii"),
+    "mvp_pointwise_mfma_splitk_plan": ("i", "iiii"),
+    "mvp_pointwise_mfma_splitk_scratch_bytes": ("q", "iiiii"),
+    "mvp_pointwise_max_backward_scratch_bytes": ("q", "iiii"),
+    "mvp_share_gather_sum_lds_bytes": ("q", "ii"),
+    "mvp_dense_edge_conv_scratch_bytes": ("q", "iiiii"),
+    "mvp_ref_layernorm_backward_scratch_bytes": ("q", "ii"),
+    "mvp_edge_bn_scratch_bytes": ("q", "ii"),
+}
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "f": ctypes.c_float,
-       "q": ctypes.c_longlong}
+       "q": ctypes.c_longlong, "s": ctypes.c_char_p}
 
 ABI_VERSION = 24  # MVP_ABI_VERSION of include/mvpops.h this binding was written against
 
@@ -98,40 +120,10 @@ def load():
             "`make -C mvp_benchmark_amd/csrc`. There is no CPU fallback."
             % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    lib.mvp_abi_version.restype = ctypes.c_int
-    lib.mvp_last_hip_error.restype = ctypes.c_char_p
-    lib.mvp_emd_scratch_bytes.restype = ctypes.c_longlong
-    lib.mvp_emd_scratch_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
-    lib.mvp_emd_configure.restype = ctypes.c_int
-    lib.mvp_emd_configure.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    lib.mvp_fps_scratch_bytes.restype = ctypes.c_longlong
-    lib.mvp_fps_cluster_scratch_bytes.restype = ctypes.c_longlong
-    lib.mvp_fps_cluster_scratch_bytes.argtypes = [ctypes.c_int]
-    lib.mvp_fps_scratch_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
-    lib.mvp_chamfer_scratch_bytes.restype = ctypes.c_longlong
-    lib.mvp_chamfer_scratch_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    lib.mvp_knn_scratch_bytes.restype = ctypes.c_longlong
-    lib.mvp_knn_scratch_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    lib.mvp_scatter_scratch_bytes.restype = ctypes.c_longlong
-    lib.mvp_scatter_scratch_bytes.argtypes = [ctypes.c_int] * 4
-    lib.mvp_pointwise_wgrad_scratch_bytes.restype = ctypes.c_longlong
-    lib.mvp_pointwise_wgrad_scratch_bytes.argtypes = [ctypes.c_int] * 4
-    lib.mvp_pointwise_wgrad_mfma_scratch_bytes.restype = ctypes.c_longlong
-    lib.mvp_pointwise_wgrad_mfma_scratch_bytes.argtypes = [ctypes.c_int] * 5
-    lib.mvp_pointwise_mfma_splitk_plan.restype = ctypes.c_int
-    lib.mvp_pointwise_mfma_splitk_plan.argtypes = [ctypes.c_int] * 4
-    lib.mvp_pointwise_mfma_splitk_scratch_bytes.restype = ctypes.c_longlong
-    lib.mvp_pointwise_mfma_splitk_scratch_bytes.argtypes = [ctypes.c_int] * 5
-    lib.mvp_pointwise_max_backward_scratch_bytes.restype = ctypes.c_longlong
-    lib.mvp_pointwise_max_backward_scratch_bytes.argtypes = [ctypes.c_int] * 4
-    lib.mvp_share_gather_sum_lds_bytes.restype = ctypes.c_longlong
-    lib.mvp_share_gather_sum_lds_bytes.argtypes = [ctypes.c_int] * 2
-    lib.mvp_dense_edge_conv_scratch_bytes.restype = ctypes.c_longlong
-    lib.mvp_dense_edge_conv_scratch_bytes.argtypes = [ctypes.c_int] * 5
-    lib.mvp_ref_layernorm_backward_scratch_bytes.restype = ctypes.c_longlong
-    lib.mvp_ref_layernorm_backward_scratch_bytes.argtypes = [ctypes.c_int] * 2
-    lib.mvp_edge_bn_scratch_bytes.restype = ctypes.c_longlong
-    lib.mvp_edge_bn_scratch_bytes.argtypes = [ctypes.c_int] * 2
+    for name, (ret, sig) in HOST_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = _CT[ret]
+        fn.argtypes = [_CT[k] for k in sig]
     for name, sig in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype = ctypes.c_int
@@ -196,9 +188,14 @@ def call(name, device, *args):
         raise MvpOpsError("%s failed: %s" % (name, detail))
 
 
+def _query(name, *ints):
+    """One host-only entry point of HOST_SIGNATURES on int arguments."""
+    return int(getattr(load(), name)(*map(int, ints)))
+
+
 def emd_scratch_bytes(b, n, iters=None):
     """Scratch of mvp_emd_forward (the same for any number of rounds)."""
-    return int(load().mvp_emd_scratch_bytes(int(b), int(n)))
+    return _query("mvp_emd_scratch_bytes", b, n)
 
 
 class EmdPlan(ctypes.Structure):
@@ -241,73 +238,67 @@ def emd_records(scratch, nbytes, b):
 
 
 def fps_cluster_scratch_bytes(b):
-    return int(load().mvp_fps_cluster_scratch_bytes(int(b)))
+    return _query("mvp_fps_cluster_scratch_bytes", b)
 
 
 def fps_scratch_bytes(b, n):
-    return int(load().mvp_fps_scratch_bytes(int(b), int(n)))
+    return _query("mvp_fps_scratch_bytes", b, n)
 
 
 def knn_scratch_bytes(b, n, m):
     """Scratch of mvp_knn_sorted (n candidates, m queries per cloud)."""
-    return int(load().mvp_knn_scratch_bytes(int(b), int(n), int(m)))
+    return _query("mvp_knn_scratch_bytes", b, n, m)
 
 
 def chamfer_scratch_bytes(b, n, m):
-    return int(load().mvp_chamfer_scratch_bytes(int(b), int(n), int(m)))
+    return _query("mvp_chamfer_scratch_bytes", b, n, m)
 
 
 def scatter_scratch_bytes(b, n_dst, m_src, r):
     """Scratch of the *_grad_ws entry points (0: shape not covered, they run the plain kernels)."""
-    return int(load().mvp_scatter_scratch_bytes(int(b), int(n_dst), int(m_src), int(r)))
+    return _query("mvp_scatter_scratch_bytes", b, n_dst, m_src, r)
 
 
 def pointwise_wgrad_scratch_bytes(b, cin, cout, length):
     """Scratch of mvp_pointwise_wgrad (0: shape not covered)."""
-    return int(load().mvp_pointwise_wgrad_scratch_bytes(int(b), int(cin), int(cout), int(length)))
+    return _query("mvp_pointwise_wgrad_scratch_bytes", b, cin, cout, length)
 
 
 def pointwise_wgrad_mfma_scratch_bytes(b, cin, cout, length, with_bias):
     """Scratch of mvp_pointwise_wgrad_mfma (0: shape not covered)."""
-    return int(load().mvp_pointwise_wgrad_mfma_scratch_bytes(int(b), int(cin), int(cout), int(length), int(with_bias)))
+    return _query("mvp_pointwise_wgrad_mfma_scratch_bytes", b, cin, cout, length, with_bias)
 
 
 def pointwise_mfma_splitk_plan(b, cin, cout, length):
     """Suggested k_chunk of mvp_pointwise_mfma_splitk for a reduction of cin into cout rows (0: do not split).  No GPU needed."""
-    return int(load().mvp_pointwise_mfma_splitk_plan(int(b), int(cin), int(cout), int(length)))
+    return _query("mvp_pointwise_mfma_splitk_plan", b, cin, cout, length)
 
 
 def pointwise_mfma_splitk_scratch_bytes(b, cin, cout, length, k_chunk):
     """Scratch of mvp_pointwise_mfma_splitk (0: shape or chunk refused)."""
-    return int(load().mvp_pointwise_mfma_splitk_scratch_bytes(int(b), int(cin), int(cout), int(length), int(k_chunk)))
+    return _query("mvp_pointwise_mfma_splitk_scratch_bytes", b, cin, cout, length, k_chunk)
 
 
 def pointwise_max_backward_scratch_bytes(b, cin, cout, length):
     """Scratch of mvp_pointwise_max_backward's staged weight gradient (0: not covered, it gathers directly)."""
-    return int(load().mvp_pointwise_max_backward_scratch_bytes(int(b), int(cin), int(cout), int(length)))
+    return _query("mvp_pointwise_max_backward_scratch_bytes", b, cin, cout, length)
 
 
 def dense_edge_conv_scratch_bytes(b, g, layers, k, n):
     """Scratch of mvp_dense_edge_conv_grad's weight gradient (0: shape not covered)."""
-    return int(load().mvp_dense_edge_conv_scratch_bytes(int(b), int(g), int(layers), int(k), int(n)))
+    return _query("mvp_dense_edge_conv_scratch_bytes", b, g, layers, k, n)
 
 
 def ref_layernorm_backward_scratch_bytes(rows, d):
     """Scratch of mvp_ref_layernorm_backward's ga / gb (0: shape refused or no rows).  No GPU needed."""
-    return int(load().mvp_ref_layernorm_backward_scratch_bytes(int(rows), int(d)))
+    return _query("mvp_ref_layernorm_backward_scratch_bytes", rows, d)
 
 
 def edge_bn_scratch_bytes(b, c):
     """Scratch of mvp_edge_bn_stats and mvp_edge_bn_relu_max_backward (0: shape refused).  No GPU needed."""
-    return int(load().mvp_edge_bn_scratch_bytes(int(b), int(c)))
+    return _query("mvp_edge_bn_scratch_bytes", b, c)
 
 
 def exported_symbols():
     """All entry points include/mvpops.h declares."""
-    return ["mvp_abi_version", "mvp_last_hip_error", "mvp_emd_scratch_bytes", "mvp_emd_configure", "mvp_chamfer_scratch_bytes", "mvp_knn_scratch_bytes", "mvp_fps_scratch_bytes", "mvp_fps_cluster_scratch_bytes",
-            "mvp_scatter_scratch_bytes", "mvp_pointwise_wgrad_scratch_bytes", "mvp_pointwise_wgrad_mfma_scratch_bytes",
-            "mvp_pointwise_mfma_splitk_plan", "mvp_pointwise_mfma_splitk_scratch_bytes",
-            "mvp_pointwise_max_backward_scratch_bytes", "mvp_share_gather_sum_lds_bytes",
-            "mvp_dense_edge_conv_scratch_bytes", "mvp_ref_layernorm_backward_scratch_bytes",
-            "mvp_edge_bn_scratch_bytes"] \
-        + list(SIGNATURES)
+    return list(HOST_SIGNATURES) + list(SIGNATURES)

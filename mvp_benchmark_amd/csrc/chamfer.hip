@@ -387,7 +387,7 @@ extern "C" int mvp_chamfer_forward_sorted(int b, int n, int m, const float *xyz1
     return mvp_chamfer_forward(b, n, m, xyz1, xyz2, dist1, dist2, idx1, idx2, stream);
   if (!xyz1 || !xyz2 || !dist1 || !dist2 || !idx1 || !idx2 || !scratch) return MVP_EBADARG;
   if (scratch_bytes < mvp_chamfer_scratch_bytes(b, n, m)) return MVP_EBADARG;
-  if ((reinterpret_cast<uintptr_t>(scratch) & 15) != 0) return MVP_EBADARG;
+  if (misaligned(scratch)) return MVP_EBADARG;
   if (b > 65535) return MVP_EBADSHAPE;
   cs_sort_launch(b, n, m, xyz1, xyz2, reinterpret_cast<char *>(scratch), as_stream(stream));
   // One query per lane: a wave's 64 consecutive sorted queries make the

@@ -21,4 +21,12 @@ int check_launch(const char *what);
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
+// The entry points' argument guards (host side).  An optional pointer passes the alignment test when it is NULL; a site
+// that requires the pointer says so in a guard of its own, in the order its tests pin.
+inline bool misaligned(const void *p, uintptr_t mask = 15) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+inline bool bad_eps(float eps) { return !(eps >= 0.f) || !__builtin_isfinite(eps); }
+inline bool scratch_short(const void *scratch, long long have, long long need) {
+  return !scratch || misaligned(scratch) || have < need;
+}
+
 }  // namespace mvp

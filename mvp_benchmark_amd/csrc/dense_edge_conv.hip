@@ -381,14 +381,12 @@ extern "C" long long mvp_dense_edge_conv_scratch_bytes(int b, int g, int layers,
   return bytes > 4 ? bytes : 4;            // layers == 0 or an empty batch need none; 0 stays "not covered"
 }
 
-static bool de_misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
-
 extern "C" int mvp_dense_edge_conv(int b, int g, int layers, int k, int n, const float *a, const float *nb,
                                    const int *idx, const float *ctr, const float *w, float *out, int *arg,
                                    void *stream) {
   if (!de_shape_ok(b, g, layers, k, n)) return MVP_EBADSHAPE;
   if (b == 0 || n == 0) return MVP_OK;
-  if (!a || !nb || !idx || !out || !arg || (layers > 0 && (!ctr || !w)) || de_misaligned(nb)) return MVP_EBADARG;
+  if (!a || !nb || !idx || !out || !arg || (layers > 0 && (!ctr || !w)) || misaligned(nb)) return MVP_EBADARG;
   const dim3 grid((n + kDeThreads - 1) / kDeThreads, b);
   hipStream_t st = as_stream(stream);
 #define MVP_DE_FWD(G, L) \
@@ -404,7 +402,7 @@ extern "C" int mvp_dense_edge_conv_grad(int b, int g, int layers, int k, int n, 
                                         float *grad_w, void *scratch, long long scratch_bytes, void *stream) {
   if (!de_shape_ok(b, g, layers, k, n)) return MVP_EBADSHAPE;
   if (b == 0 || n == 0) return MVP_OK;
-  if (!a || !nb || !idx || !arg || !grad_out || !grad_a || de_misaligned(nb)) return MVP_EBADARG;
+  if (!a || !nb || !idx || !arg || !grad_out || !grad_a || misaligned(nb)) return MVP_EBADARG;
   if (layers > 0 && (!ctr || !w || !grad_ctr || !grad_w || !scratch ||
                      scratch_bytes < mvp_dense_edge_conv_scratch_bytes(b, g, layers, k, n)))
     return MVP_EBADARG;

@@ -21,7 +21,7 @@
 // Chan's update.  The backward sums go the same way.  No atomics, nothing passes between workgroups inside a launch: the
 // same bits on every run.  double costs nothing here: the kernels wait for memory.
 // In the map and the backward sweeps a lane owns groups of four columns (float4) and walks k, kEbAhead loads in flight.
-// Non-finite values and the dead channel: include/mvpops.h.
+// Non-finite values and the dead channel: include/mvpops.h.  The entry points' guards: common.h.
 #include "common.h"
 #include "wave.h"
 
@@ -38,6 +38,7 @@ constexpr int kEbMaxK = 64;
 // The map, shared by every kernel below: the backward pass's mask y > 0 has the forward's bits.
 __device__ __forceinline__ float ebn_y(float z, float mean, float scale, float beta) { return __builtin_fmaf(z - mean, scale, beta); }
 __device__ __forceinline__ float ebn_relu(float y) { return y <= 0.f ? 0.f : y; }      // a NaN is not <= 0: it stays
+__device__ __forceinline__ float ebn_xhat(float z, float mean, float invstd) { return (z - mean) * invstd; }
 __device__ __forceinline__ float4 ebn_zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 
 // The sum over the workgroup of one double per lane, in every lane: wave_sum's tree, then the waves in order.  Holds two
@@ -236,8 +237,8 @@ __global__ __launch_bounds__(kEbThreads) void ebn_backward_sums_kernel(int c, in
         if (j0 + u < k) {
           const float4 gy = ebn_gy4(v[u], w[u], pool, at, j0 + u, mean, scale, bt);
           s1 += ebn_sum4(gy);
-          s2 += ((double)(gy.x * ((v[u].x - mean) * invstd)) + (double)(gy.y * ((v[u].y - mean) * invstd))) +
-                ((double)(gy.z * ((v[u].z - mean) * invstd)) + (double)(gy.w * ((v[u].w - mean) * invstd)));
+          s2 += ((double)(gy.x * ebn_xhat(v[u].x, mean, invstd)) + (double)(gy.y * ebn_xhat(v[u].y, mean, invstd))) +
+                ((double)(gy.z * ebn_xhat(v[u].z, mean, invstd)) + (double)(gy.w * ebn_xhat(v[u].w, mean, invstd)));
         }
       }
     }
@@ -307,10 +308,10 @@ __global__ __launch_bounds__(kEbThreads) void ebn_backward_gz_kernel(int c, int 
           const float4 gy = ebn_gy4(v[u], w[u], pool, at, j0 + u, mean, scale, bt);
           float4 o;
           if (BATCH) {
-            o = make_float4(scale * ((gy.x - c1) - ((v[u].x - mean) * invstd) * c2),
-                            scale * ((gy.y - c1) - ((v[u].y - mean) * invstd) * c2),
-                            scale * ((gy.z - c1) - ((v[u].z - mean) * invstd) * c2),
-                            scale * ((gy.w - c1) - ((v[u].w - mean) * invstd) * c2));
+            o = make_float4(scale * ((gy.x - c1) - ebn_xhat(v[u].x, mean, invstd) * c2),
+                            scale * ((gy.y - c1) - ebn_xhat(v[u].y, mean, invstd) * c2),
+                            scale * ((gy.z - c1) - ebn_xhat(v[u].z, mean, invstd) * c2),
+                            scale * ((gy.w - c1) - ebn_xhat(v[u].w, mean, invstd) * c2));
           } else {
             o = make_float4(scale * gy.x, scale * gy.y, scale * gy.z, scale * gy.w);
           }
@@ -325,7 +326,6 @@ static bool ebn_shape_ok(int b, int c, int k, int n) {
   return b >= 1 && c >= 1 && k >= 1 && k <= kEbMaxK && n >= 4 && (n & 3) == 0 && (long long)k * n < 2147483648LL &&
          (long long)b * c < 2147483648LL;
 }
-static bool ebn_off(const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }      // NULL is aligned
 // {partials: [b c][2] double} {coef: [c][2] float}, the second part on a 16-byte address
 static long long ebn_part_bytes(int b, int c) { return (long long)b * c * 2 * (long long)sizeof(double); }
 
@@ -341,10 +341,10 @@ extern "C" long long mvp_edge_bn_scratch_bytes(int b, int c) {
 extern "C" int mvp_edge_bn_stats(int b, int c, int k, int n, const float *z, float eps, float *stats, float *var,
                                  void *scratch, long long scratch_bytes, void *stream) {
   if (!ebn_shape_ok(b, c, k, n)) return MVP_EBADSHAPE;
-  if (!(eps >= 0.f) || !__builtin_isfinite(eps)) return MVP_EBADARG;
-  if (ebn_off(z, 15)) return MVP_EBADARG;
+  if (bad_eps(eps)) return MVP_EBADARG;
+  if (misaligned(z)) return MVP_EBADARG;
   if (!z || !stats || !var) return MVP_EBADARG;
-  if (!scratch || ebn_off(scratch, 15) || scratch_bytes < mvp_edge_bn_scratch_bytes(b, c)) return MVP_EBADARG;
+  if (scratch_short(scratch, scratch_bytes, mvp_edge_bn_scratch_bytes(b, c))) return MVP_EBADARG;
   hipStream_t st = as_stream(stream);
   double *part = static_cast<double *>(scratch);
   const int nvec = (int)(((long long)k * n) >> 2);
@@ -363,7 +363,7 @@ extern "C" int mvp_edge_bn_stats(int b, int c, int k, int n, const float *z, flo
 extern "C" int mvp_edge_bn_relu_max(int b, int c, int k, int n, const float *z, const float *stats, const float *gamma,
                                     const float *beta, float *r, float *pooled, unsigned char *arg, void *stream) {
   if (!ebn_shape_ok(b, c, k, n)) return MVP_EBADSHAPE;
-  if (ebn_off(z, 15) || ebn_off(r, 15) || ebn_off(pooled, 15) || ebn_off(arg, 3)) return MVP_EBADARG;
+  if (misaligned(z) || misaligned(r) || misaligned(pooled) || misaligned(arg, 3)) return MVP_EBADARG;
   if (!z || !stats || !gamma || !beta || !pooled || !arg) return MVP_EBADARG;
   const dim3 grid((unsigned)(b * c)), block(kEbThreads);
   hipStream_t st = as_stream(stream);
@@ -379,11 +379,11 @@ extern "C" int mvp_edge_bn_relu_max_backward(int b, int c, int k, int n, int bat
                                              const float *g_r, const float *g_pool, float *gz, float *ggamma, float *gbeta,
                                              void *scratch, long long scratch_bytes, void *stream) {
   if (!ebn_shape_ok(b, c, k, n)) return MVP_EBADSHAPE;
-  if (ebn_off(z, 15) || ebn_off(g_r, 15) || ebn_off(g_pool, 15) || ebn_off(gz, 15) || ebn_off(arg, 3)) return MVP_EBADARG;
+  if (misaligned(z) || misaligned(g_r) || misaligned(g_pool) || misaligned(gz) || misaligned(arg, 3)) return MVP_EBADARG;
   if (!g_r && !g_pool) return MVP_EBADARG;
   if (!z || !stats || !gamma || !beta || !gz || (g_pool && !arg)) return MVP_EBADARG;
   const bool sums = batch_stats || ggamma || gbeta;
-  if (sums && (!scratch || ebn_off(scratch, 15) || scratch_bytes < mvp_edge_bn_scratch_bytes(b, c))) return MVP_EBADARG;
+  if (sums && scratch_short(scratch, scratch_bytes, mvp_edge_bn_scratch_bytes(b, c))) return MVP_EBADARG;
   const dim3 grid((unsigned)(b * c)), block(kEbThreads);
   hipStream_t st = as_stream(stream);
   double *part = static_cast<double *>(scratch);

@@ -309,7 +309,7 @@ extern "C" int mvp_edge_mlp_max(int b, int c, int n, int k, int stages, int w1, 
   if (!em_plan(b, c, n, k, stages, widths, pl)) return MVP_EBADSHAPE;
   if (b == 0 || n == 0) return MVP_OK;
   if (!x || !idx || !w || !scale || !shift || !out) return MVP_EBADARG;
-  if ((reinterpret_cast<uintptr_t>(w) & 15) != 0) return MVP_EBADARG;      // the weights' rows are read 16 bytes at a time
+  if (misaligned(w)) return MVP_EBADARG;      // the weights' rows are read 16 bytes at a time
   const int lds = (pl.rows + kEmGatherRows) * (32 * pl.ncb + kEmPad) * 4;
   if (hipFuncSetAttribute(reinterpret_cast<const void *>(edge_mlp_max_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                           lds) != hipSuccess)

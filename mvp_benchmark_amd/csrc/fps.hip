@@ -742,7 +742,7 @@ extern "C" int mvp_furthest_point_sampling_sorted(int b, int n, int m, const flo
     return mvp_furthest_point_sampling(b, n, m, points, temp, idx, stream);
   if (!points || !temp || !idx || !scratch) return MVP_EBADARG;
   if (scratch_bytes < mvp_fps_scratch_bytes(b, n)) return MVP_EBADARG;
-  if ((reinterpret_cast<uintptr_t>(scratch) & 15) != 0) return MVP_EBADARG;
+  if (misaligned(scratch)) return MVP_EBADARG;
   const int p = (n + 1023) / 1024;
   const int pp = p <= 6 ? 6 : p <= 8 ? 8 : p <= 12 ? 12 : 16;
   float4 *sorted = reinterpret_cast<float4 *>(scratch);

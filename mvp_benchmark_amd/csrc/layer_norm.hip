@@ -21,6 +21,7 @@
 // launch: the same bits on every run.
 // Non-finite rows: a NaN or an Inf in a row makes its mean or its centred values NaN, hence std, U and all d entries of y
 // and gz; no other row is touched, and a column of ga / gb is NaN if a contributing row is.
+// Host side: the guards are common.h's (misaligned, bad_eps, scratch_short), NV is picked once, in MVP_LN_LAUNCH.
 #include "common.h"
 #include "wave.h"
 
@@ -262,27 +263,30 @@ __global__ __launch_bounds__(64 * kLnSumParts) void ln_slab_sum_kernel(int nslab
 static bool ln_shape_ok(int rows, int d) {
   return rows >= 0 && d >= 4 && d <= kLnMaxD && (d & 3) == 0 && (long long)rows * d < 2147483648LL;
 }
-static bool ln_misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }      // NULL is aligned
 
 }  // namespace mvp
 
 using namespace mvp;
 
+// KERNEL<NV> for NV = ceil(d / 256) float4 a lane; `grid`, `block` and `st` are the caller's.
+#define MVP_LN_LAUNCH(KERNEL, LDS, ...)                                                    \
+  switch ((d + 255) / 256) {                                                               \
+    case 1: hipLaunchKernelGGL(KERNEL<1>, grid, block, LDS, st, __VA_ARGS__); break;       \
+    case 2: hipLaunchKernelGGL(KERNEL<2>, grid, block, LDS, st, __VA_ARGS__); break;       \
+    case 3: hipLaunchKernelGGL(KERNEL<3>, grid, block, LDS, st, __VA_ARGS__); break;       \
+    default: hipLaunchKernelGGL(KERNEL<4>, grid, block, LDS, st, __VA_ARGS__); break;      \
+  }
+
 extern "C" int mvp_ref_layernorm(int rows, int d, const float *x, const float *delta, const float *a, const float *b,
                                  float eps, float *sum, float *y, float *stats, void *stream) {
   if (!ln_shape_ok(rows, d)) return MVP_EBADSHAPE;
-  if (!(eps >= 0.f) || !__builtin_isfinite(eps)) return MVP_EBADARG;
-  if (ln_misaligned(x) || ln_misaligned(delta) || ln_misaligned(sum) || ln_misaligned(y)) return MVP_EBADARG;
+  if (bad_eps(eps)) return MVP_EBADARG;
+  if (misaligned(x) || misaligned(delta) || misaligned(sum) || misaligned(y)) return MVP_EBADARG;
   if (rows == 0) return MVP_OK;
   if (!x || !a || !b || !y || (delta && !sum)) return MVP_EBADARG;
   const dim3 grid((unsigned)ln_grid(rows)), block(kLnThreads);
   hipStream_t st = as_stream(stream);
-  switch ((d + 255) / 256) {
-    case 1: hipLaunchKernelGGL(ln_forward_kernel<1>, grid, block, 0, st, rows, d, x, delta, a, b, eps, sum, y, stats); break;
-    case 2: hipLaunchKernelGGL(ln_forward_kernel<2>, grid, block, 0, st, rows, d, x, delta, a, b, eps, sum, y, stats); break;
-    case 3: hipLaunchKernelGGL(ln_forward_kernel<3>, grid, block, 0, st, rows, d, x, delta, a, b, eps, sum, y, stats); break;
-    default: hipLaunchKernelGGL(ln_forward_kernel<4>, grid, block, 0, st, rows, d, x, delta, a, b, eps, sum, y, stats); break;
-  }
+  MVP_LN_LAUNCH(ln_forward_kernel, 0, rows, d, x, delta, a, b, eps, sum, y, stats);
   return check_launch("mvp_ref_layernorm");
 }
 
@@ -295,25 +299,18 @@ extern "C" int mvp_ref_layernorm_backward(int rows, int d, const float *z, const
                                           const float *gres, const float *stats, float eps, float *gz, float *ga,
                                           float *gb, void *scratch, long long scratch_bytes, void *stream) {
   if (!ln_shape_ok(rows, d)) return MVP_EBADSHAPE;
-  if (!(eps >= 0.f) || !__builtin_isfinite(eps)) return MVP_EBADARG;
-  if (ln_misaligned(z) || ln_misaligned(gy) || ln_misaligned(gres) || ln_misaligned(gz)) return MVP_EBADARG;
+  if (bad_eps(eps)) return MVP_EBADARG;
+  if (misaligned(z) || misaligned(gy) || misaligned(gres) || misaligned(gz)) return MVP_EBADARG;
   if (rows == 0) return MVP_OK;      // nothing to add: ga / gb of an empty batch are the caller's zeros
   if (!z || !a || !gy || !stats || !gz) return MVP_EBADARG;
   const bool cols = ga || gb;
-  if (cols && (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15) != 0 ||
-               scratch_bytes < mvp_ref_layernorm_backward_scratch_bytes(rows, d)))
-    return MVP_EBADARG;
+  if (cols && scratch_short(scratch, scratch_bytes, mvp_ref_layernorm_backward_scratch_bytes(rows, d))) return MVP_EBADARG;
   const int nb = ln_grid(rows);
   const dim3 grid((unsigned)nb), block(kLnThreads);
   const size_t lds = cols ? (size_t)kLnWaves * 2 * d * sizeof(float) : 0;
   float *slabs = cols ? static_cast<float *>(scratch) : nullptr;
   hipStream_t st = as_stream(stream);
-  switch ((d + 255) / 256) {
-    case 1: hipLaunchKernelGGL(ln_backward_kernel<1>, grid, block, lds, st, rows, d, z, a, gy, gres, stats, eps, gz, slabs); break;
-    case 2: hipLaunchKernelGGL(ln_backward_kernel<2>, grid, block, lds, st, rows, d, z, a, gy, gres, stats, eps, gz, slabs); break;
-    case 3: hipLaunchKernelGGL(ln_backward_kernel<3>, grid, block, lds, st, rows, d, z, a, gy, gres, stats, eps, gz, slabs); break;
-    default: hipLaunchKernelGGL(ln_backward_kernel<4>, grid, block, lds, st, rows, d, z, a, gy, gres, stats, eps, gz, slabs); break;
-  }
+  MVP_LN_LAUNCH(ln_backward_kernel, lds, rows, d, z, a, gy, gres, stats, eps, gz, slabs);
   if (cols) {
     const int rc = check_launch("mvp_ref_layernorm_backward");
     if (rc != MVP_OK) return rc;

@@ -712,7 +712,7 @@ extern "C" int mvp_knn_sorted(int b, int n, int m, int nsample, const float *xyz
     return mvp_knn(b, n, m, nsample, xyz, new_xyz, idx, dist2, stream);
   if (!xyz || !new_xyz || !idx || !dist2 || !scratch) return MVP_EBADARG;
   if (scratch_bytes < mvp_knn_scratch_bytes(b, n, m)) return MVP_EBADARG;
-  if ((reinterpret_cast<uintptr_t>(scratch) & 15) != 0) return MVP_EBADARG;
+  if (misaligned(scratch)) return MVP_EBADARG;
   if (b > 65535) return MVP_EBADSHAPE;
   char *sc = reinterpret_cast<char *>(scratch);
   int *fix_cnt = reinterpret_cast<int *>(sc + (size_t)b * (cs_side_bytes(m) + cs_side_bytes(n)));
@@ -742,7 +742,7 @@ extern "C" int mvp_topk_gram(int b, int n, int k, const float *dot, const float 
   if (k <= kWave && n <= 16384) {
     dim3 wgrid((n + kTwWaves * kTwRows - 1) / (kTwWaves * kTwRows), b);
     const size_t wlds = (size_t)((n + 3) & ~3) * 4;
-    if (n % 4 == 0 && (reinterpret_cast<uintptr_t>(dot) & 15) == 0)
+    if (n % 4 == 0 && !misaligned(dot))
       hipLaunchKernelGGL(topk_gram_wave_kernel<4>, wgrid, dim3(kTwWaves * kWave), wlds, as_stream(stream), n, k, dot,
                          sq, idx);
     else

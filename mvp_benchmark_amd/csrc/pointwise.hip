@@ -215,7 +215,7 @@ extern "C" int mvp_pointwise_dgrad(int b, int cin, int cout, int len, const floa
                                    void *stream) {
   if (b <= 0 || cin <= 0 || cout <= 0 || cin > 64 || cout > 64 || len <= 0 || len % 4 != 0 || b > 65535) return MVP_EBADSHAPE;
   if (!weight || !gy || !gx) return MVP_EBADARG;
-  if (((reinterpret_cast<uintptr_t>(gy) | reinterpret_cast<uintptr_t>(gx)) & 15) != 0) return MVP_EBADARG;
+  if (misaligned(gy) || misaligned(gx)) return MVP_EBADARG;
   hipStream_t st = as_stream(stream);
   const dim3 grid((len / 2 + 255) / 256, b), block(256);
   // (one pass over gy when all input channels fit the accumulators; 64 channels take two)
@@ -232,7 +232,7 @@ extern "C" int mvp_pointwise_wgrad(int b, int cin, int cout, int len, const floa
   const long long need = mvp_pointwise_wgrad_scratch_bytes(b, cin, cout, len);
   if (need == 0) return MVP_EBADSHAPE;
   if (!x || !gy || !gw || !scratch || scratch_bytes < need) return MVP_EBADARG;
-  if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gy)) & 15) != 0) return MVP_EBADARG;
+  if (misaligned(x) || misaligned(gy)) return MVP_EBADARG;
   const PwPlan pl = pw_plan(cin, cout);
   const int nrun = (len + kPwTile * kPwRun - 1) / (kPwTile * kPwRun);
   const long long npart = pw_blocks(b, len);

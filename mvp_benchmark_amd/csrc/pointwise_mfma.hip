@@ -733,8 +733,7 @@ extern "C" int mvp_pointwise_wgrad_mfma_ex(int b, int cin, int cout, int len, co
   const long long need = mvp_pointwise_wgrad_mfma_scratch_bytes(b, cin, cout, len, with_bias);
   if (need == 0) return MVP_EBADSHAPE;
   if (!x || !gy || !gw || !scratch || scratch_bytes < need) return MVP_EBADARG;
-  if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gy) | reinterpret_cast<uintptr_t>(gymask)) & 15) != 0)
-    return MVP_EBADARG;
+  if (misaligned(x) || misaligned(gy) || misaligned(gymask)) return MVP_EBADARG;
   int spc, sps, splits;
   wgrad_plan(b, cin, cout, len, spc, sps, splits);
   hipStream_t st = as_stream(stream);
@@ -795,11 +794,11 @@ static int pw_ex_check(int b, int cin, int cout, int len, const float *x, const 
     return MVP_OK;
   }
   if (!x || !w || !y) return MVP_EBADARG;
-  if ((reinterpret_cast<uintptr_t>(x) & 15) != 0 || (reinterpret_cast<uintptr_t>(xmask) & 15) != 0) return MVP_EBADARG;
+  if (misaligned(x) || misaligned(xmask)) return MVP_EBADARG;
   if (ldw == 0) ldw = w_kmajor ? cout : cin;                    // dense rows
   if (ldw < (w_kmajor ? cout : cin)) return MVP_EBADARG;
-  if (w_kmajor && ((cout & 3) != 0 || (ldw & 3) != 0 || (reinterpret_cast<uintptr_t>(w) & 15) != 0)) return MVP_EBADARG;
-  if (!w_kmajor && (ldw & 3) == 0 && (reinterpret_cast<uintptr_t>(w) & 15) != 0) return MVP_EBADARG;
+  if (w_kmajor && ((cout & 3) != 0 || (ldw & 3) != 0 || misaligned(w))) return MVP_EBADARG;
+  if (!w_kmajor && (ldw & 3) == 0 && misaligned(w)) return MVP_EBADARG;
   return MVP_OK;
 }
 
@@ -880,7 +879,7 @@ extern "C" int mvp_pointwise_mfma_splitk(int b, int cin, int cout, int len, cons
   if (rc != MVP_OK || empty) return rc;
   const long long need = mvp_pointwise_mfma_splitk_scratch_bytes(b, cin, cout, len, k_chunk);
   if (need == 0) return MVP_EBADSHAPE;
-  if (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15) != 0 || scratch_bytes < need) return MVP_EBADARG;
+  if (scratch_short(scratch, scratch_bytes, need)) return MVP_EBADARG;
   hipStream_t st = as_stream(stream);
   const bool big = cout > 64, narrow = splitk_tile_n(len) == 64;
   const long long nwg = pw_grid(cout, pw_tile(cout), len, splitk_tile_n(len), (long long)splits * b);
@@ -912,7 +911,7 @@ extern "C" int mvp_pointwise_mfma_splitk(int b, int cin, int cout, int len, cons
 #undef MVP_SK_TILE
 #undef MVP_SK
 #undef MVP_SK_
-  const int vec_io = ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(residual)) & 15) == 0;
+  const int vec_io = !misaligned(y) && !misaligned(residual);
   hipLaunchKernelGGL(pointwise_splitk_reduce_kernel, dim3((unsigned)nred), dim3(256), 0, st, quads, cout, len, splits, partial,
                      bias, bias_per_cloud ? cout : 0, residual, flags, vec_io, y);
   return check_launch("mvp_pointwise_mfma_splitk");
@@ -928,11 +927,11 @@ extern "C" int mvp_pointwise_mfma_max(int b, int cin, int cout, int len, const f
   if ((len & 3) != 0 || b > 65535) return MVP_EBADSHAPE;
   if (b == 0) return MVP_OK;
   if (!x || !w || !val || !idx || !keys) return MVP_EBADARG;
-  if (keys_bytes < (long long)b * cout * 8 || (reinterpret_cast<uintptr_t>(keys) & 7) != 0) return MVP_EBADARG;
-  if ((reinterpret_cast<uintptr_t>(x) & 15) != 0) return MVP_EBADARG;
+  if (keys_bytes < (long long)b * cout * 8 || misaligned(keys, 7)) return MVP_EBADARG;
+  if (misaligned(x)) return MVP_EBADARG;
   if (ldw == 0) ldw = cin;
   if (ldw < cin) return MVP_EBADARG;
-  if ((ldw & 3) == 0 && (reinterpret_cast<uintptr_t>(w) & 15) != 0) return MVP_EBADARG;
+  if ((ldw & 3) == 0 && misaligned(w)) return MVP_EBADARG;
   hipStream_t st = as_stream(stream);
   if (hipMemsetAsync(keys, 0, (size_t)b * cout * 8, st) != hipSuccess) return MVP_ELAUNCH;
   const bool big = cout > 64;

@@ -39,6 +39,47 @@ def test_library_exports_every_declared_symbol():
         assert lib.mvp_emd_configure(0, -1, _lib.EMD_DEFAULT_SPLIT, 16) == 0
 
 
+def test_binding_tables_match_every_prototype_of_the_header():
+    """Every prototype of include/mvpops.h against the binding's two tables: the return type and, parameter by parameter,
+    the kind ctypes converts to (* -> p, long long -> q, float -> f, int -> i).  A launching entry point returns int and
+    ends in the stream pointer, which SIGNATURES leaves out; a host-only one is in HOST_SIGNATURES with its return kind."""
+    from mvp_benchmark_amd import _lib
+    header = open(os.path.join(ROOT, "include", "mvpops.h")).read()
+    header = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    header = re.sub(r"//[^\n]*", " ", header)
+    protos = re.findall(r"(?m)^(int|long long|const char \*)\s*(mvp_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header)
+    assert len(protos) == len(set(p[1] for p in protos)) == len(re.findall(r"\bmvp_[a-z0-9_]+\s*\(", header))
+
+    def kind(param):
+        param = " ".join(param.split())
+        if "*" in param:
+            return "p"
+        for text, k in (("long long ", "q"), ("float ", "f"), ("int ", "i")):
+            if param.startswith(text):
+                return k
+        raise AssertionError("parameter %r" % param)
+
+    ret_kind = {"int": "i", "long long": "q", "const char *": "s"}
+    seen = {}
+    for ret, name, params in protos:
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        seen[name] = (ret_kind[ret], "".join(kind(p) for p in params), params)
+    assert not set(_lib.SIGNATURES) & set(_lib.HOST_SIGNATURES)
+    assert set(seen) == set(_lib.SIGNATURES) | set(_lib.HOST_SIGNATURES)
+    for name, (ret, kinds, params) in seen.items():
+        if name in _lib.SIGNATURES:
+            assert ret == "i" and params[-1].split() == ["void", "*stream"], name
+            assert kinds == _lib.SIGNATURES[name] + "p", name
+        else:
+            assert (ret, kinds) == _lib.HOST_SIGNATURES[name], name
+    assert len(_lib.HOST_SIGNATURES) >= 18 and len(_lib.SIGNATURES) >= 51       # the parser did not come back empty
+    # what load() hands ctypes is the tables, nothing else
+    lib = _lib.load()
+    for name, (ret, kinds, _) in seen.items():
+        fn = getattr(lib, name)
+        assert fn.restype is _lib._CT[ret] and list(fn.argtypes) == [_lib._CT[k] for k in kinds], name
+
+
 def test_argument_guards_need_no_gpu():
     """Shape guards return error codes before anything is launched."""
     from mvp_benchmark_amd import _lib

@@ -6,7 +6,8 @@ the transformer's fused LayerNorm + residual sums (mvp_benchmark_amd.registratio
 the transformer alone, the training step's peak memory per route, and the two kernels alone with their bytes/s; then DGCNN's
 BatchNorm + ReLU + max over the neighbours as kernels in training (mvp_benchmark_amd.registration.EDGE_BN): emb_nn forward +
 backward, the whole step, peak memory per route, and the three entry points alone at the four stage shapes.
-   python tools/bench_dcp.py            (MVP_BENCH_REPS: timed repetitions, MVP_BENCH_AB_ROUNDS: alternations, at least 5)"""
+   python tools/bench_dcp.py            (MVP_BENCH_REPS: timed repetitions, MVP_BENCH_AB_ROUNDS: alternations, at least 5;
+                                         MVP_LIB=<other libmvpops.so> for an A/B of two builds)"""
 import os, sys, time, types
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REG = os.path.join(ROOT, "registration")
@@ -15,8 +16,10 @@ import torch
 import dcp
 import train_utils as tu
 
-import mvp_benchmark_amd.registration as reg_ops
 from mvp_benchmark_amd import _lib
+if os.environ.get("MVP_LIB"):          # A/B: another build of the library
+    _lib.LIB_PATH = os.path.abspath(os.environ["MVP_LIB"])
+import mvp_benchmark_amd.registration as reg_ops
 
 REPS = int(os.environ.get("MVP_BENCH_REPS", "10"))
 ROUNDS = max(5, int(os.environ.get("MVP_BENCH_AB_ROUNDS", "5")))
