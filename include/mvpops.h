@@ -43,7 +43,7 @@ extern "C" {
 #define MVP_ELAUNCH (-3)
 
 /* ABI version of this header; bumped on any signature change. */
-#define MVP_ABI_VERSION 24
+#define MVP_ABI_VERSION 25
 int mvp_abi_version(void);
 
 /* hipGetErrorString of the last launch failure seen on the calling thread
@@ -508,6 +508,27 @@ int mvp_dense_edge_conv_grad(int b, int g, int layers, int k, int n, const float
 int mvp_edge_mlp_max(int b, int c, int n, int k, int stages, int w1, int w2, int w3, int w4,
                      const float *x, const int *idx, const float *w, const float *scale,
                      const float *shift, float *out, void *stream);
+
+/* ABI 25.  Multi-head attention of DCP's transformer in inference (registration/models/dcp.py: MultiHeadedAttention; the
+ * reference, dcp.py:26-33, 210-229, runs q k^T, the division by sqrt(d), the softmax, the second product and a transposed copy as
+ * five steps over a (b, h, nq, nk) score tensor) as one kernel.  Per (cloud, head t, query row i):
+ *   s_ij = scale * <q_i, k_j>,      out_i = sum_j softmax_j(s_ij) v_j
+ * q and out are (b, nq, h d), k and v (b, nk, h d), contiguous float32, head t in the columns t d .. t d + d of a row: the
+ * layout the module's nn.Linear projections write and read, no head transpose or reshape copy exists on this route.
+ * Covered: d in {32, 64, 96, 128}; any nq, nk >= 1 (partial tiles on both axes); b, h >= 1; every tensor below 2^31
+ * elements; all four pointers on 16-byte addresses.  b == 0 or nq == 0 launches nothing and returns MVP_OK; anything
+ * else outside the coverage (a negative size, h < 1, nk == 0, another d, a NULL or misaligned pointer) is MVP_EBADARG,
+ * with nothing launched and no output written.
+ * Arithmetic: flash-style, tiles of 32 keys with an online softmax (running maximum and sum per query); both products run
+ * on v_mfma_f32_32x32x2_f32 (float32 in, float32 accumulate, a k-ordered fmaf chain); the weights are
+ * exp2((s_ij - m) log2 e) with the hardware's exp2, out = O / l in IEEE division.  No score or weight is written to global
+ * memory; no scratch, no atomics: every output is a fixed expression, the same bits on every run, and a row's bits do not
+ * depend on which other query rows are in the call.
+ * Non-finite values: the maximum masks nothing, so a NaN in query row i makes output row i NaN in that head's columns and
+ * no other row; a NaN in key j, or in a column of value j, makes every row of that (cloud, head) NaN (value: in that
+ * column); no other (cloud, head) is touched.  +-inf inputs are not specified.  Forward only. */
+int mvp_attention_forward(int b, int h, int nq, int nk, int d, const float *q, const float *k, const float *v,
+                          float scale, float *out, void *stream);
 
 /* ------------------------------------------- grouped-feature MLP on MFMA */
 

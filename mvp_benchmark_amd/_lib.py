@@ -70,6 +70,7 @@ SIGNATURES = {
     "mvp_edge_bn_stats": "iiiipfpppq",
     "mvp_edge_bn_relu_max": "iiiippppppp",
     "mvp_edge_bn_relu_max_backward": "iiiiipppppppppppq",
+    "mvp_attention_forward": "iiiiipppfp",
 }
 # The host-only entry points (no stream, nothing launched): name -> (return kind, argument kinds); s = const char *.
 # With SIGNATURES this is every prototype of include/mvpops.h (tests/test_host.py checks both against the header).
@@ -96,7 +97,7 @@ HOST_SIGNATURES = {
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "f": ctypes.c_float,
        "q": ctypes.c_longlong, "s": ctypes.c_char_p}
 
-ABI_VERSION = 24  # MVP_ABI_VERSION of include/mvpops.h this binding was written against
+ABI_VERSION = 25  # MVP_ABI_VERSION of include/mvpops.h this binding was written against
 
 # default of mvp_emd_configure's `split` knob (csrc/emd.hip: emd_knobs)
 EMD_DEFAULT_SPLIT = 5

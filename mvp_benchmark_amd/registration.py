@@ -3,10 +3,11 @@ composition written in torch for CPU / float64 tensors (the float64 equivalence 
 
   Kabsch rotation      kabsch_rotation, svd3, svd3_kabsch_backward             mvp_kabsch_svd3
   DeepGMR              rri_features, gmm_params, gmm_register                  mvp_rri_features, mvp_gmm_params[_backward]
-  DCP's switches       EDGE_MLP, LAYER_NORM, EDGE_BN (all off) and routes(), the one way to flip them for a block
+  DCP's switches       EDGE_MLP, LAYER_NORM, EDGE_BN, FUSED_ATTENTION (all off) and routes(), the one way to flip them for a block
   DGCNN, inference     edge_mlp_max                                            mvp_edge_mlp_max
   the transformer      ref_layer_norm (LayerNorm + the residual sum)           mvp_ref_layernorm[_backward]
   DGCNN, training      bn_relu_max (BatchNorm + ReLU + max over k)             mvp_edge_bn_stats, mvp_edge_bn_relu_max[_backward]
+  attention, inference fused_attention (softmax(q k^T scale) v, all heads)     mvp_attention_forward
 
 `kabsch_rotation(H)` replaces the per-sample loop of the reference's SVDHead
 (registration/models/dcp.py:360-373, registration/model_utils.py:229-240):
@@ -276,22 +277,24 @@ def gmm_register(pi_s, mu_s, mu_t, sigma_t):
 
 
 # ----------------------------------------------------------------------------------------------- DCP's switches
-# registration/models/dcp.py reads these where it chooses a route (DGCNN._route, LayerNorm.forward).  Plain module attributes,
-# all off: a route changes a summation order, and a default flips in a change of its own.
+# registration/models/dcp.py reads these where it chooses a route (DGCNN._route, LayerNorm.forward,
+# MultiHeadedAttention._route).  Plain module attributes, all off: a route changes a summation order, and a default flips in a
+# change of its own.
 
 EDGE_MLP = False           # True: DGCNN.forward takes the fused route in eval mode (float32 CUDA, nothing requires grad)
 LAYER_NORM = False         # True: LayerNorm.forward and the transformer's residual sums take ref_layer_norm
 EDGE_BN = False            # True: DGCNN.forward runs stages 1-4 through bn_relu_max when training or a gradient is needed
+FUSED_ATTENTION = False    # True: MultiHeadedAttention.forward takes fused_attention where nothing asks for a gradient (float32 CUDA)
 
 
 @contextlib.contextmanager
-def routes(*, edge_mlp=None, layer_norm=None, edge_bn=None):
-    """Set the named switches (EDGE_MLP, LAYER_NORM, EDGE_BN) for the length of a `with` block: None leaves a switch as it is,
-    and every switch named gets back the value it had on the way in, also when the block raises.  Blocks nest.
+def routes(*, edge_mlp=None, layer_norm=None, edge_bn=None, fused_attention=None):
+    """Set the named switches (EDGE_MLP, LAYER_NORM, EDGE_BN, FUSED_ATTENTION) for the length of a `with` block: None leaves a
+    switch as it is, and every switch named gets back the value it had on the way in, also when the block raises.  Blocks nest.
         with registration.routes(edge_mlp=True, layer_norm=True, edge_bn=True): ...
     The switches are module attributes, so this is process-global and not thread-safe: every model in the process sees them,
     and two threads inside blocks of their own restore each other's values."""
-    asked = {"EDGE_MLP": edge_mlp, "LAYER_NORM": layer_norm, "EDGE_BN": edge_bn}
+    asked = {"EDGE_MLP": edge_mlp, "LAYER_NORM": layer_norm, "EDGE_BN": edge_bn, "FUSED_ATTENTION": fused_attention}
     module = globals()
     before = {name: module[name] for name, on in asked.items() if on is not None}
     module.update({name: bool(asked[name]) for name in before})
@@ -570,3 +573,44 @@ def bn_relu_max(z, weight, bias, running_mean, running_var, training, momentum, 
         stats = torch.stack((running_mean, (1 / torch.sqrt(running_var.double() + eps)).float()), dim=1).contiguous()
     r, pooled, _, _ = BnReluMax.apply(z, weight, bias, stats, eps, want_r)
     return r, pooled
+
+
+# ------------------------------------------------------------------------------ multi-head attention in inference (DCP)
+# registration/models/dcp.py: MultiHeadedAttention between its projections -- q k^T, the scale, the softmax and the product
+# with v for all heads as one kernel (mvp_attention_forward, csrc/attention.hip), on the projections' own (B, N, heads * d)
+# layout: no score tensor, no head transpose.
+
+ATTENTION_WIDTHS = (32, 64, 96, 128)     # the head widths mvp_attention_forward covers
+
+
+def _attention_reference(q, k, v, heads, divisor):
+    """The composition MultiHeadedAttention.forward runs, op for op: split into heads, softmax(q k^T / divisor) v, the heads
+    back side by side (the module divides by sqrt(d_k))."""
+    b, d = q.size(0), q.size(2) // heads
+    split = lambda t: t.reshape(b, -1, heads, d).transpose(1, 2)
+    q, k, v = split(q), split(k), split(v)
+    weights = F.softmax(q @ k.transpose(-2, -1) / divisor, dim=-1)
+    return (weights @ v).transpose(1, 2).reshape(b, -1, heads * d)
+
+
+def fused_attention(q, k, v, heads, scale=None):
+    """q (B, Nq, heads * d), k and v (B, Nk, heads * d), head t in the columns t d .. t d + d (what the module's projections
+    produce) -> (B, Nq, heads * d): per (cloud, head, query row i)
+        s_ij = scale * <q_i, k_j>,   out_i = sum_j softmax_j(s_ij) v_j,        scale = 1 / sqrt(d) unless given.
+    float32 CUDA contiguous tensors on 16-byte addresses with d in {32, 64, 96, 128}, Nk >= 1 and fewer than 2^31 elements run
+    mvp_attention_forward (flash-style on v_mfma_f32_32x32x2_f32: no (B, heads, Nq, Nk) tensor exists); CPU tensors, float64,
+    any other d, a non-contiguous or misaligned view and Nk == 0 take the module's composition written in torch.
+    Forward only: no input may require grad while grad mode is on."""
+    assert not (torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v))), "fused_attention has no backward"
+    assert q.dim() == k.dim() == v.dim() == 3 and k.shape == v.shape and q.shape[0] == k.shape[0] and q.shape[2] == k.shape[2]
+    assert heads >= 1 and q.shape[2] % heads == 0
+    d = q.shape[2] // heads
+    divisor = math.sqrt(d) if scale is None else 1.0 / scale      # the composition divides, as the module does
+    scale = 1.0 / divisor if scale is None else scale
+    B, nq, nk = q.shape[0], q.shape[1], k.shape[1]
+    fits = d in ATTENTION_WIDTHS and nk >= 1 and max(q.numel(), k.numel()) < 2 ** 31
+    if not (fits and _kernel_reads((q, k, v), aligned=(q, k, v))):
+        return _attention_reference(q, k, v, heads, divisor)
+    out = torch.empty_like(q)
+    call("mvp_attention_forward", q.device, B, heads, nq, nk, d, q.detach(), k.detach(), v.detach(), scale, out)
+    return out

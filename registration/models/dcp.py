@@ -15,8 +15,10 @@ the 1x1 convolutions are library GEMMs -- except on DGCNN's opt-in inference rou
 maxima as one kernel and conv5 as one MFMA GEMM.  The transformer's LayerNorm and residual sums have an opt-in route of
 their own (mvp_benchmark_amd.registration.LAYER_NORM): every `x + f(...)` followed by a norm is one kernel, each way.
 DGCNN in training has a third (mvp_benchmark_amd.registration.EDGE_BN): BatchNorm, ReLU and the max over the neighbours of
-stages 1-4 as kernels, forward and backward.  Each module has ONE dataflow: the switches are read in two places, DGCNN._route
-and LayerNorm.forward (mvp_benchmark_amd.registration.routes sets them for a block).
+stages 1-4 as kernels, forward and backward.  Attention in inference has a fourth (mvp_benchmark_amd.registration.FUSED_ATTENTION):
+softmax(q k^T / sqrt(d_k)) v for all heads as one kernel between the projections, no score tensor and no head transpose.  Each
+module has ONE dataflow: the switches are read in three places, DGCNN._route, LayerNorm.forward and
+MultiHeadedAttention._route (mvp_benchmark_amd.registration.routes sets them for a block).
 """
 import copy
 import math
@@ -96,7 +98,26 @@ class MultiHeadedAttention(nn.Module):
         proto = nn.Linear(d_model, d_model)
         self.linears = nn.ModuleList([copy.deepcopy(proto) for _ in range(4)])
 
+    def _route(self, query, memory):
+        """forward(query, memory)'s route, decided once and launching nothing: a pure function of the switch, grad mode and who
+        requires grad (the two inputs, the module's parameters), the inputs' device, dtype and shape.
+          "fused"     the three projections, softmax(q k^T / sqrt(d_k)) v for all heads as one kernel
+                      (mvp_benchmark_amd.registration.fused_attention), the output projection: FUSED_ATTENTION is on, both
+                      inputs are float32 CUDA and 3-D, d_k is a width the kernel covers and nothing asks for a gradient (the
+                      route has no backward).
+          "composed"  everything else: the switch off, training with gradients, CPU, float64."""
+        if not _reg.FUSED_ATTENTION or self.d_k not in _reg.ATTENTION_WIDTHS:
+            return "composed"
+        if not all(t.dim() == 3 and t.is_cuda and t.dtype == torch.float32 for t in (query, memory)):
+            return "composed"
+        wanted = torch.is_grad_enabled() and (query.requires_grad or memory.requires_grad
+                                              or any(p.requires_grad for p in self.parameters()))
+        return "composed" if wanted else "fused"
+
     def forward(self, query, memory):
+        if self._route(query, memory) == "fused":
+            q, k, v = self.linears[0](query), self.linears[1](memory), self.linears[2](memory)
+            return self.linears[3](_reg.fused_attention(q, k, v, self.h))
         b = query.size(0)
         split = lambda t: t.view(b, -1, self.h, self.d_k).transpose(1, 2)
         q = split(self.linears[0](query))

@@ -5,9 +5,12 @@ backward (training step without the optimizer) timings, with the op-layer split 
 the transformer's fused LayerNorm + residual sums (mvp_benchmark_amd.registration.LAYER_NORM): eval forward, forward + backward,
 the transformer alone, the training step's peak memory per route, and the two kernels alone with their bytes/s; then DGCNN's
 BatchNorm + ReLU + max over the neighbours as kernels in training (mvp_benchmark_amd.registration.EDGE_BN): emb_nn forward +
-backward, the whole step, peak memory per route, and the three entry points alone at the four stage shapes.
+backward, the whole step, peak memory per route, and the three entry points alone at the four stage shapes; then multi-head
+attention as one kernel in inference (mvp_benchmark_amd.registration.FUSED_ATTENTION): eval forward, the transformer alone, one
+attention block alone, the eval forward's peak memory per route, and the kernel alone in TFLOP/s.
    python tools/bench_dcp.py            (MVP_BENCH_REPS: timed repetitions, MVP_BENCH_AB_ROUNDS: alternations, at least 5;
-                                         MVP_LIB=<other libmvpops.so> for an A/B of two builds)"""
+                                         MVP_LIB=<other libmvpops.so> for an A/B of two builds;
+                                         MVP_BENCH_ONLY=attention: the attention block alone)"""
 import os, sys, time, types
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REG = os.path.join(ROOT, "registration")
@@ -104,6 +107,57 @@ def fwd_bwd():
     loss = net(src, tgt, T_gt)[0]
     loss.mean().backward()
 
+
+def attention_block():
+    """The A/B of mvp_benchmark_amd.registration.FUSED_ATTENTION (default off), every other switch off, both routes in this one
+    process: the eval forward, the transformer alone, one attention block alone at cfg 5's shape (the five composed steps
+    against the one kernel, projections left out), the eval forward's peak memory per route, and the kernel alone in TFLOP/s."""
+    import math
+    H, D, PEAK_F32 = dcp.HEADS, dcp.EMB_DIMS // dcp.HEADS, 157.3
+    net.eval()
+    with torch.no_grad():
+        f_a, f_b = (net.emb_nn(c.transpose(1, 2).contiguous()) for c in (src, tgt))
+    ga = torch.Generator().manual_seed(8)
+    qa, ka, va = (torch.randn(B, N, H * D, generator=ga).to(dev) for _ in range(3))
+    oa = torch.empty_like(qa)
+    flop = 4.0 * B * H * N * N * D
+
+    def pointer_alone():
+        with torch.no_grad():
+            return net.pointer(f_a, f_b)
+
+    def block_alone():
+        with torch.no_grad():
+            if reg_ops.FUSED_ATTENTION:
+                return reg_ops.fused_attention(qa, ka, va, H)
+            return reg_ops._attention_reference(qa, ka, va, H, math.sqrt(D))
+
+    print("# fused attention A/B: %s; torch %s; %d alternations x %d repetitions, median ms [min .. max]; 6 attention blocks per "
+          "forward over (%d, %d, %d, %d, %d); one block = %.0f GFLOP, float32 MFMA peak %.1f TFLOP/s = %.2f ms" % (
+              torch.cuda.get_device_name(0), torch.__version__, ROUNDS, REPS, B, H, N, N, D, flop / 1e9, PEAK_F32,
+              flop / PEAK_F32 / 1e9), flush=True)
+    faster = alternate("fused_attention", (("eval forward", fwd, False, None),
+                                           ("transformer alone, eval forward", pointer_alone, False, None),
+                                           ("one attention block alone (%d, %d, %d, %d, %d)" % (B, H, N, N, D), block_alone, False, None)),
+                       48, "composed / fused %(ratio).3f   composed - fused %(diff)6.2f ms   fused faster in every alternation: %(faster)s")
+    print("  criterion (fused faster than composed in every alternation of the eval forward): %s" % (
+        "met" if faster["eval forward"] else "NOT met -- the switch stays off either way"), flush=True)
+    for on in (False, True):
+        with reg_ops.routes(fused_attention=on):
+            fwd(); torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            fwd(); torch.cuda.synchronize()
+            print("  eval forward, %s route: torch.cuda.max_memory_allocated %.2f GB" % (
+                "fused" if on else "composed", torch.cuda.max_memory_allocated() / 1e9), flush=True)
+    t = sorted(timed(lambda: _lib.call("mvp_attention_forward", dev, B, H, N, N, D, qa, ka, va, 1 / math.sqrt(D), oa), 20)
+               for _ in range(5))[2]
+    print("  mvp_attention_forward alone at (%d, %d, %d, %d, %d): %7.3f ms  %6.1f TFLOP/s = %4.1f %% of the float32 MFMA peak "
+          "(FLOP = 4 b h nq nk d)" % (B, H, N, N, D, t, flop / t / 1e9, flop / t / 1e9 / PEAK_F32 * 100), flush=True)
+
+
+if os.environ.get("MVP_BENCH_ONLY") == "attention":      # this block alone (the whole tool takes minutes)
+    attention_block()
+    sys.exit(0)
 
 net.eval()
 ms_f = timed(fwd)
@@ -296,3 +350,6 @@ for C, which in ((64, "stages 1 and 2"), (128, "stage 3"), (256, "stage 4")):
     kernels_alone(entries, T, 10, "    %-74s")
     del ze, gre, gpe, re_, gze
     torch.cuda.empty_cache()
+
+# ---- multi-head attention as one kernel in inference (mvp_benchmark_amd.registration.FUSED_ATTENTION, default off)
+attention_block()

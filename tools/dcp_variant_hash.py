@@ -1,8 +1,9 @@
-"""Digest of DCP's norm and edge kernels of one library build on fixed seeded inputs:
+"""Digest of DCP's norm, edge and attention kernels of one library build on fixed seeded inputs:
    python tools/dcp_variant_hash.py [lib.so]
 One line per case, a sha1 over the raw bytes of every output of mvp_edge_bn_stats, mvp_edge_bn_relu_max (with and without
 r), mvp_edge_bn_relu_max_backward (batch and running statistics; g_r / g_pool each absent once), mvp_ref_layernorm (with and
-without delta), mvp_ref_layernorm_backward (with and without gres, with and without ga / gb) and mvp_edge_mlp_max.  Two
+without delta), mvp_ref_layernorm_backward (with and without gres, with and without ga / gb), mvp_edge_mlp_max and
+mvp_attention_forward (every shape of tests/attention_cases.py, the four random families and the two exact ones).  Two
 builds whose kernels compute the same bits print the same lines (the -m gpu tests hold the default library to its bounds)."""
 import sys, os, hashlib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -11,7 +12,7 @@ import torch
 from mvp_benchmark_amd import _lib
 if len(sys.argv) > 1:
     _lib.LIB_PATH = os.path.abspath(sys.argv[1])
-import edge_bn_cases, edge_mlp_cases, layer_norm_cases
+import attention_cases, edge_bn_cases, edge_mlp_cases, layer_norm_cases
 
 dev = torch.device("cuda:0")
 LOOPING = (4 * 2048 + 5, 4)                      # tests/test_gpu_layer_norm.py: more rows than the grid has waves
@@ -99,8 +100,23 @@ def edge_mlp(shape, pattern):
     dg.line("edge_mlp %s %s" % (shape, pattern))
 
 
+def attention(shape):
+    B, H, Nq, Nk, D = shape
+    dg = Digest()
+    cases = [attention_cases.inputs(shape, family) for family in attention_cases.FAMILIES]
+    cases += [attention_cases.exact_inputs(shape, family)[:3] for family in attention_cases.EXACT_FAMILIES]
+    for q, k, v in cases:
+        q, k, v = (attention_cases.packed(t).to(dev) for t in (q, k, v))
+        out = nan(B, Nq, H * D)
+        _lib.call("mvp_attention_forward", dev, B, H, Nq, Nk, D, q, k, v, attention_cases.default_scale(shape), out)
+        dg.add(out)
+    dg.line("attention %s" % (shape,))
+
+
 for shape in edge_bn_cases.SHAPES:
     edge_bn(shape)
 for rows, d in [(rows, d) for rows in layer_norm_cases.ROWS for d in layer_norm_cases.DIMS] + [(257, d) for d in EDGE_D] + [LOOPING]:
     layer_norm(rows, d)
 edge_mlp(edge_mlp_cases.SHAPES[1], "random")
+for shape in attention_cases.SHAPES:
+    attention(shape)
