@@ -341,6 +341,15 @@ __global__ __launch_bounds__(kCgThreads) void nm_distance_grad_lds_kernel(
 
 using namespace mvp;
 
+template <int Q>   // queries per lane; both directions in one launch, sized by the larger side
+static void nm_distance_launch(int b, int n, int m, const float *xyz1, const float *xyz2, float *dist1, float *dist2,
+                               int *idx1, int *idx2, hipStream_t stream) {
+  const int big = n > m ? n : m;
+  dim3 grid((big + kCdThreads * Q - 1) / (kCdThreads * Q), b, 2);
+  hipLaunchKernelGGL(nm_distance_kernel<Q>, grid, dim3(kCdThreads), 0, stream, n, m, xyz1, xyz2, dist1, dist2, idx1,
+                     idx2);
+}
+
 extern "C" int mvp_chamfer_forward(int b, int n, int m, const float *xyz1,
                                    const float *xyz2, float *dist1,
                                    float *dist2, int *idx1, int *idx2,
@@ -350,25 +359,14 @@ extern "C" int mvp_chamfer_forward(int b, int n, int m, const float *xyz1,
   if (n == 0 || m == 0) return MVP_EBADSHAPE;  // no nearest neighbour exists
   if (!xyz1 || !xyz2 || !dist1 || !dist2 || !idx1 || !idx2) return MVP_EBADARG;
   if (b > 65535) return MVP_EBADSHAPE;
-  const int big = n > m ? n : m;
   // Q queries per lane: 4 when there is enough work to fill 256 CUs anyway.
-  const long long work = (long long)b * big;
-  if (work >= 4LL * 256 * kCdThreads * 4) {
-    dim3 grid((big + kCdThreads * 4 - 1) / (kCdThreads * 4), b, 2);
-    hipLaunchKernelGGL(nm_distance_kernel<4>, grid, dim3(kCdThreads), 0,
-                       as_stream(stream), n, m, xyz1, xyz2, dist1, dist2, idx1,
-                       idx2);
-  } else if (work >= 2LL * 256 * kCdThreads * 2) {
-    dim3 grid((big + kCdThreads * 2 - 1) / (kCdThreads * 2), b, 2);
-    hipLaunchKernelGGL(nm_distance_kernel<2>, grid, dim3(kCdThreads), 0,
-                       as_stream(stream), n, m, xyz1, xyz2, dist1, dist2, idx1,
-                       idx2);
-  } else {
-    dim3 grid((big + kCdThreads - 1) / kCdThreads, b, 2);
-    hipLaunchKernelGGL(nm_distance_kernel<1>, grid, dim3(kCdThreads), 0,
-                       as_stream(stream), n, m, xyz1, xyz2, dist1, dist2, idx1,
-                       idx2);
-  }
+  const long long work = (long long)b * (n > m ? n : m);
+  if (work >= 4LL * 256 * kCdThreads * 4)
+    nm_distance_launch<4>(b, n, m, xyz1, xyz2, dist1, dist2, idx1, idx2, as_stream(stream));
+  else if (work >= 2LL * 256 * kCdThreads * 2)
+    nm_distance_launch<2>(b, n, m, xyz1, xyz2, dist1, dist2, idx1, idx2, as_stream(stream));
+  else
+    nm_distance_launch<1>(b, n, m, xyz1, xyz2, dist1, dist2, idx1, idx2, as_stream(stream));
   return check_launch("mvp_chamfer_forward");
 }
 
@@ -385,9 +383,8 @@ extern "C" int mvp_chamfer_forward_sorted(int b, int n, int m, const float *xyz1
   // (break-even measured at about 4096 x 4096 pairs per cloud)
   if (b <= 0 || n < 2048 || m < 2048 || (long long)n * m < (1ll << 24) || (n > m ? n : m) > (1 << 30))
     return mvp_chamfer_forward(b, n, m, xyz1, xyz2, dist1, dist2, idx1, idx2, stream);
-  if (!xyz1 || !xyz2 || !dist1 || !dist2 || !idx1 || !idx2 || !scratch) return MVP_EBADARG;
-  if (scratch_bytes < mvp_chamfer_scratch_bytes(b, n, m)) return MVP_EBADARG;
-  if (misaligned(scratch)) return MVP_EBADARG;
+  if (!xyz1 || !xyz2 || !dist1 || !dist2 || !idx1 || !idx2) return MVP_EBADARG;
+  if (scratch_short(scratch, scratch_bytes, mvp_chamfer_scratch_bytes(b, n, m))) return MVP_EBADARG;
   if (b > 65535) return MVP_EBADSHAPE;
   cs_sort_launch(b, n, m, xyz1, xyz2, reinterpret_cast<char *>(scratch), as_stream(stream));
   // One query per lane: a wave's 64 consecutive sorted queries make the

@@ -532,27 +532,16 @@ static int launch_fps(int b, int n, int m, const float *dataset, float *temp,
 #define MVP_FPS_CASE(PP)                                                      \
   hipLaunchKernelGGL((fps_kernel<PP, WITH_DIST>), grid, block, 0, stream, n, m, \
                      log2bs, dataset, temp, idx)
-  if (n >= (1 << 20)) {
-    return MVP_EBADSHAPE;  // index field of the packed key is 20 bits
-  } else if (p <= 1) {
-    MVP_FPS_CASE(1);
-  } else if (p <= 2) {
-    MVP_FPS_CASE(2);
-  } else if (p <= 3) {
-    MVP_FPS_CASE(3);
-  } else if (p <= 4) {
-    MVP_FPS_CASE(4);
-  } else if (p <= 6) {
-    MVP_FPS_CASE(6);
-  } else if (p <= 8) {
-    MVP_FPS_CASE(8);
-  } else if (p <= 12) {
-    MVP_FPS_CASE(12);
-  } else if (p <= 16) {
-    MVP_FPS_CASE(16);
-  } else {
-    MVP_FPS_CASE(0);
-  }
+  if (n >= (1 << 20)) return MVP_EBADSHAPE;  // index field of the packed key is 20 bits
+  if (p <= 1) MVP_FPS_CASE(1);
+  else if (p <= 2) MVP_FPS_CASE(2);
+  else if (p <= 3) MVP_FPS_CASE(3);
+  else if (p <= 4) MVP_FPS_CASE(4);
+  else if (p <= 6) MVP_FPS_CASE(6);
+  else if (p <= 8) MVP_FPS_CASE(8);
+  else if (p <= 12) MVP_FPS_CASE(12);
+  else if (p <= 16) MVP_FPS_CASE(16);
+  else MVP_FPS_CASE(0);
 #undef MVP_FPS_CASE
   return MVP_OK;
 }
@@ -732,6 +721,13 @@ extern "C" long long mvp_fps_scratch_bytes(int b, int n) {
   return (long long)b * 16384 * 16;  // one float4 per (padded) point of the largest supported cloud
 }
 
+template <int P>   // points per lane of 1024: the cloud sorted and padded to 1024 * P points, then the kernel
+static void fps_sorted_launch(int b, int n, int m, const float *points, float4 *sorted, float *temp, int *idx,
+                              hipStream_t st) {
+  cs_sort_points_launch(b, n, 1024 * P, points, sorted, st);
+  hipLaunchKernelGGL(fps_sorted_kernel<P>, dim3(b), dim3(1024), 0, st, n, m, points, sorted, temp, idx);
+}
+
 extern "C" int mvp_furthest_point_sampling_sorted(int b, int n, int m, const float *points, float *temp,
                                                   int *idx, void *scratch, long long scratch_bytes,
                                                   void *stream) {
@@ -740,21 +736,15 @@ extern "C" int mvp_furthest_point_sampling_sorted(int b, int n, int m, const flo
   // (measured: 3.22 -> 2.99 ms at (64, 16384 -> 2048); no gain at 8192 points and below)
   if (b <= 0 || m <= 1 || n <= 4096 || n > 16384)
     return mvp_furthest_point_sampling(b, n, m, points, temp, idx, stream);
-  if (!points || !temp || !idx || !scratch) return MVP_EBADARG;
-  if (scratch_bytes < mvp_fps_scratch_bytes(b, n)) return MVP_EBADARG;
-  if (misaligned(scratch)) return MVP_EBADARG;
+  if (!points || !temp || !idx) return MVP_EBADARG;
+  if (scratch_short(scratch, scratch_bytes, mvp_fps_scratch_bytes(b, n))) return MVP_EBADARG;
   const int p = (n + 1023) / 1024;
-  const int pp = p <= 6 ? 6 : p <= 8 ? 8 : p <= 12 ? 12 : 16;
   float4 *sorted = reinterpret_cast<float4 *>(scratch);
   hipStream_t st = as_stream(stream);
-  cs_sort_points_launch(b, n, 1024 * pp, points, sorted, st);
-#define MVP_FPS_SORTED(PP) \
-  hipLaunchKernelGGL((fps_sorted_kernel<PP>), dim3(b), dim3(1024), 0, st, n, m, points, sorted, temp, idx)
-  if (pp == 6) MVP_FPS_SORTED(6);
-  else if (pp == 8) MVP_FPS_SORTED(8);
-  else if (pp == 12) MVP_FPS_SORTED(12);
-  else MVP_FPS_SORTED(16);
-#undef MVP_FPS_SORTED
+  if (p <= 6) fps_sorted_launch<6>(b, n, m, points, sorted, temp, idx, st);
+  else if (p <= 8) fps_sorted_launch<8>(b, n, m, points, sorted, temp, idx, st);
+  else if (p <= 12) fps_sorted_launch<12>(b, n, m, points, sorted, temp, idx, st);
+  else fps_sorted_launch<16>(b, n, m, points, sorted, temp, idx, st);
   return check_launch("mvp_furthest_point_sampling_sorted");
 }
 

@@ -86,8 +86,60 @@ __device__ __forceinline__ void knn_reheap(float *hd, int *hi, int t, int k) {
   }
 }
 
-// knn_kernel, knn_cuda.cu:58-95: admission by strict `<` against the heap
-// root (:83), reheap swapping on equality (:34), final heap_sort (:44-53).
+// The reference's heap sequence (knn_cuda.cu:26-53,80-90), stated once for the three kernels that replay it
+// (knn_kernel, knn_fix_kernel, topk_gram_kernel): every slot starts at (d, 0) (:75-78); a candidate is admitted
+// by strict `<` against the root (:83) -- the caller's test, against the root heap_admit returned last -- and
+// takes the root's place; the reheap swaps on equality (:34); a heap sort ends it (:44-53).
+// (knn_fix_kernel fills its column itself: there a wave shares one column and lane s writes slot s.)
+template <int T>
+__device__ __forceinline__ void heap_fill(float *hd, int *hi, int t, int k, float d) {
+  for (int i = 0; i < k; ++i) {
+    hd[i * T + t] = d;
+    hi[i * T + t] = 0;
+  }
+}
+
+template <int T>
+__device__ __forceinline__ float heap_admit(float *hd, int *hi, int t, int k, float d, int id) {
+  hd[t] = d;
+  hi[t] = id;
+  knn_reheap<T>(hd, hi, t, k);
+  return hd[t];
+}
+
+template <int T>
+__device__ __forceinline__ void heap_sort(float *hd, int *hi, int t, int k) {
+  for (int i = k - 1; i > 0; i--) {
+    const float tf = hd[t];
+    hd[t] = hd[i * T + t];
+    hd[i * T + t] = tf;
+    const int ti = hi[t];
+    hi[t] = hi[i * T + t];
+    hi[i * T + t] = ti;
+    knn_reheap<T>(hd, hi, t, i);
+  }
+}
+
+// The survivors of a screen of 32 candidates (bit c of `mask`: key(base + c) was below the root the screen
+// started with -- a superset of what the reference admits, because the root only falls) replayed in index order
+// against the CURRENT root, so the sequence of heap operations is the reference's.  A wave runs the divergent
+// heap update max-over-lanes(survivors) times per screen instead of once per candidate that any lane admits.
+// (`base`, the screen's first candidate, is added here and not inside the functors: key and id then share one
+// sum, as the open-coded loop did; functors that each add it cost knn_kernel an instruction and an SGPR.)
+template <int T, class Key, class Id>
+__device__ __forceinline__ void heap_replay(float *hd, int *hi, int t, int k, int base, unsigned &mask, float &rootd,
+                                            Key key, Id id) {
+  while (__any(mask != 0u)) {
+    if (mask != 0u) {
+      const int c = base + __builtin_ctz(mask);
+      mask &= mask - 1u;
+      const float d = key(c);
+      if (d < rootd) rootd = heap_admit<T>(hd, hi, t, k, d, id(c));
+    }
+  }
+}
+
+// knn_kernel, knn_cuda.cu:58-95.
 template <int T>
 __global__ __launch_bounds__(T) void knn_kernel(
     int n, int m, int nsample, const float *__restrict__ xyz,
@@ -107,19 +159,12 @@ __global__ __launch_bounds__(T) void knn_kernel(
   const float *pts = xyz + (size_t)cloud * n * 3;
   const float nx = c[0], ny = c[1], nz = c[2];
 
-  for (int i = 0; i < nsample; ++i) {
-    hd[i * T + t] = 1e10f;
-    hi[i * T + t] = 0;
-  }
+  heap_fill<T>(hd, hi, t, nsample, 1e10f);
   float rootd = 1e10f;
 
   // Candidates are screened 32 at a time against the heap root the sub-tile
   // started with (branch-free, three wave-uniform ds_read_b128 per four
-  // candidates); the survivors -- a superset of what the reference admits,
-  // because the root only falls -- are then replayed in index order against
-  // the CURRENT root, so the sequence of heap operations is the reference's.
-  // A wave therefore runs the divergent heap update max-over-lanes(survivors)
-  // times per sub-tile instead of once per candidate that any lane admits.
+  // candidates); heap_replay takes the survivors.
   for (int k2 = 0; k2 < n; k2 += kQTile) {
     const int cnt = min(kQTile, n - k2);
     const int padded = (cnt + 31) / 32 * 32;
@@ -144,31 +189,13 @@ __global__ __launch_bounds__(T) void knn_kernel(
         mask |= (d2 < rootd ? 1u : 0u) << (4 * g + 2);
         mask |= (d3 < rootd ? 1u : 0u) << (4 * g + 3);
       }
-      while (__any(mask != 0u)) {
-        if (mask != 0u) {
-          const int i = sub + __builtin_ctz(mask);
-          mask &= mask - 1u;
-          const float d2 = sqdist3(nx - tile[i * 3 + 0], ny - tile[i * 3 + 1], nz - tile[i * 3 + 2]);
-          if (d2 < rootd) {
-            hd[t] = d2;
-            hi[t] = k2 + i;
-            knn_reheap<T>(hd, hi, t, nsample);
-            rootd = hd[t];
-          }
-        }
-      }
+      heap_replay<T>(
+          hd, hi, t, nsample, sub, mask, rootd,
+          [&](int i) { return sqdist3(nx - tile[i * 3 + 0], ny - tile[i * 3 + 1], nz - tile[i * 3 + 2]); },
+          [&](int i) { return k2 + i; });
     }
   }
-  // heap_sort
-  for (int i = nsample - 1; i > 0; i--) {
-    const float tf = hd[t];
-    hd[t] = hd[i * T + t];
-    hd[i * T + t] = tf;
-    const int ti = hi[t];
-    hi[t] = hi[i * T + t];
-    hi[i * T + t] = ti;
-    knn_reheap<T>(hd, hi, t, i);
-  }
+  heap_sort<T>(hd, hi, t, nsample);
   if (active) {
     int *o = idx + ((size_t)cloud * m + p) * nsample;
     float *od = dist2 + ((size_t)cloud * m + p) * nsample;
@@ -179,8 +206,8 @@ __global__ __launch_bounds__(T) void knn_kernel(
   }
 }
 
-// One WAVE per listed query: the reference's sequence of heap operations (admission in index order by strict
-// `<` against the root, reheap, final heap sort: knn_cuda.cu:26-53,80-90) with the 64 lanes screening 64
+// One WAVE per listed query: the reference's sequence of heap operations (the heap_* helpers above, on the
+// wave's own LDS column: stride 1, column 0) with the 64 lanes screening 64
 // consecutive candidates at a time against the root the step started with -- the survivors, a superset of
 // what the reference admits there, are replayed in index order against the current root.  The fix-up pass of
 // the sorted variant below: a handful of queries per million on random clouds, every query on a lattice.
@@ -214,23 +241,11 @@ __global__ __launch_bounds__(kFixWaves * 64) void knn_fix_kernel(
         const int l = (int)__builtin_ctzll(mask);
         mask &= mask - 1ull;
         const float dl = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(d), l));
-        if (dl < rootd) {   // (wave-uniform: every lane runs the same heap update on the wave's LDS column)
-          hd[0] = dl;
-          hi[0] = base + l;
-          knn_reheap<1>(hd, hi, 0, nsample);
-          rootd = hd[0];
-        }
+        // (wave-uniform: every lane runs the same heap update on the wave's LDS column)
+        if (dl < rootd) rootd = heap_admit<1>(hd, hi, 0, nsample, dl, base + l);
       }
     }
-    for (int i = nsample - 1; i > 0; i--) {   // heap_sort
-      const float tf = hd[0];
-      hd[0] = hd[i];
-      hd[i] = tf;
-      const int ti = hi[0];
-      hi[0] = hi[i];
-      hi[i] = ti;
-      knn_reheap<1>(hd, hi, 0, i);
-    }
+    heap_sort<1>(hd, hi, 0, nsample);
     if (lane < nsample) {
       idx[((size_t)cloud * m + p) * nsample + lane] = hi[lane];
       dist2[((size_t)cloud * m + p) * nsample + lane] = hd[lane];
@@ -446,10 +461,7 @@ __global__ __launch_bounds__(kFkRows) void topk_gram_kernel(
   dot += (size_t)cloud * n * n;
   sq += (size_t)cloud * n;
   const float sqi = active ? sq[row] : 0.f;
-  for (int i = 0; i < k; ++i) {
-    hd[i * kFkRows + t] = __builtin_inff();
-    hi[i * kFkRows + t] = 0;
-  }
+  heap_fill<kFkRows>(hd, hi, t, k, __builtin_inff());
   float rootd = __builtin_inff();
   for (int c0 = 0; c0 < n; c0 += kFkCols) {
     __syncthreads();
@@ -461,37 +473,16 @@ __global__ __launch_bounds__(kFkRows) void topk_gram_kernel(
     }
     if (t < kFkCols) sqc[t] = c0 + t < n ? sq[c0 + t] : __builtin_inff();   // key = +inf: never admitted
     __syncthreads();
+    const auto key = [&](int c) {
+      const float inner = -2.f * tile[t * (kFkCols + 1) + c];
+      return -((-sqc[c] - inner) - sqi);
+    };
     unsigned mask = 0u;
 #pragma unroll
-    for (int c = 0; c < kFkCols; ++c) {
-      const float inner = -2.f * tile[t * (kFkCols + 1) + c];
-      const float key = -((-sqc[c] - inner) - sqi);
-      mask |= (key < rootd ? 1u : 0u) << c;
-    }
-    while (__any(mask != 0u)) {
-      if (mask != 0u) {
-        const int c = __builtin_ctz(mask);
-        mask &= mask - 1u;
-        const float inner = -2.f * tile[t * (kFkCols + 1) + c];
-        const float key = -((-sqc[c] - inner) - sqi);
-        if (key < rootd) {
-          hd[t] = key;
-          hi[t] = c0 + c;
-          knn_reheap<kFkRows>(hd, hi, t, k);
-          rootd = hd[t];
-        }
-      }
-    }
+    for (int c = 0; c < kFkCols; ++c) mask |= (key(c) < rootd ? 1u : 0u) << c;
+    heap_replay<kFkRows>(hd, hi, t, k, 0, mask, rootd, key, [&](int c) { return c0 + c; });
   }
-  for (int i = k - 1; i > 0; i--) {  // heap sort: ascending key = descending value
-    const float tf = hd[t];
-    hd[t] = hd[i * kFkRows + t];
-    hd[i * kFkRows + t] = tf;
-    const int ti = hi[t];
-    hi[t] = hi[i * kFkRows + t];
-    hi[i * kFkRows + t] = ti;
-    knn_reheap<kFkRows>(hd, hi, t, i);
-  }
+  heap_sort<kFkRows>(hd, hi, t, k);   // ascending key = descending value
   if (active) {
     int *o = idx + ((size_t)cloud * n + row) * k;
     for (int i = 0; i < k; ++i) o[i] = hi[i * kFkRows + t];
@@ -661,6 +652,14 @@ extern "C" int mvp_ball_query(int b, int n, int m, float min_radius,
   return check_launch("mvp_ball_query");
 }
 
+template <int T>
+static void knn_launch(int b, int n, int m, int nsample, const float *xyz, const float *new_xyz, int *idx, float *dist2,
+                       hipStream_t stream) {
+  const size_t lds = kQTile * 3 * 4 + (size_t)nsample * T * 8;
+  hipLaunchKernelGGL(knn_kernel<T>, dim3((m + T - 1) / T, b), dim3(T), lds, stream, n, m, nsample, xyz, new_xyz, idx,
+                     dist2);
+}
+
 extern "C" int mvp_knn(int b, int n, int m, int nsample, const float *xyz,
                        const float *new_xyz, int *idx, float *dist2,
                        void *stream) {
@@ -671,25 +670,12 @@ extern "C" int mvp_knn(int b, int n, int m, int nsample, const float *xyz,
   if (b > 65535) return MVP_EBADSHAPE;
   // Heap columns live in LDS; block size shrinks with k so that
   // tile (12 KiB) + heaps (nsample*T*8 B) stays under 64 KiB.
-  if (nsample <= 16) {
-    constexpr int T = 256;
-    const size_t lds = kQTile * 3 * 4 + (size_t)nsample * T * 8;
-    dim3 grid((m + T - 1) / T, b);
-    hipLaunchKernelGGL(knn_kernel<T>, grid, dim3(T), lds, as_stream(stream), n,
-                       m, nsample, xyz, new_xyz, idx, dist2);
-  } else if (nsample <= 32) {
-    constexpr int T = 128;
-    const size_t lds = kQTile * 3 * 4 + (size_t)nsample * T * 8;
-    dim3 grid((m + T - 1) / T, b);
-    hipLaunchKernelGGL(knn_kernel<T>, grid, dim3(T), lds, as_stream(stream), n,
-                       m, nsample, xyz, new_xyz, idx, dist2);
-  } else {
-    constexpr int T = 64;
-    const size_t lds = kQTile * 3 * 4 + (size_t)nsample * T * 8;
-    dim3 grid((m + T - 1) / T, b);
-    hipLaunchKernelGGL(knn_kernel<T>, grid, dim3(T), lds, as_stream(stream), n,
-                       m, nsample, xyz, new_xyz, idx, dist2);
-  }
+  if (nsample <= 16)
+    knn_launch<256>(b, n, m, nsample, xyz, new_xyz, idx, dist2, as_stream(stream));
+  else if (nsample <= 32)
+    knn_launch<128>(b, n, m, nsample, xyz, new_xyz, idx, dist2, as_stream(stream));
+  else
+    knn_launch<64>(b, n, m, nsample, xyz, new_xyz, idx, dist2, as_stream(stream));
   return check_launch("mvp_knn");
 }
 
@@ -701,6 +687,14 @@ extern "C" long long mvp_knn_scratch_bytes(int b, int n, int m) {
   return (long long)b * (cs_side_bytes(m) + cs_side_bytes(n)) + knn_cnt_bytes(b) + ((long long)b * m * 4 + 15) / 16 * 16;
 }
 
+template <int KL>   // the list slots of a query, >= nsample + 1
+static void knn_sorted_launch(int b, int n, int m, int nsample, char *sc, int *idx, float *dist2, int *fix_cnt,
+                              int *fix_list, hipStream_t stream) {
+  constexpr int T = 256;
+  hipLaunchKernelGGL((knn_sorted_kernel<T, KL>), dim3((m + T - 1) / T, b), dim3(T), 0, stream, n, m, nsample, sc, idx,
+                     dist2, fix_cnt, fix_list);
+}
+
 extern "C" int mvp_knn_sorted(int b, int n, int m, int nsample, const float *xyz, const float *new_xyz, int *idx,
                               float *dist2, void *scratch, long long scratch_bytes, void *stream) {
   // small clouds / many neighbours: the exhaustive kernel (the heaps of k + 1 <= 33 entries per query fit the
@@ -710,26 +704,24 @@ extern "C" int mvp_knn_sorted(int b, int n, int m, int nsample, const float *xyz
   const bool large = (n >= 4096 && m >= 1024) || (n >= 2048 && m >= 2048);
   if (b <= 0 || !large || nsample < 1 || nsample > 32 || (n > m ? n : m) > (1 << 30))
     return mvp_knn(b, n, m, nsample, xyz, new_xyz, idx, dist2, stream);
-  if (!xyz || !new_xyz || !idx || !dist2 || !scratch) return MVP_EBADARG;
-  if (scratch_bytes < mvp_knn_scratch_bytes(b, n, m)) return MVP_EBADARG;
-  if (misaligned(scratch)) return MVP_EBADARG;
+  if (!xyz || !new_xyz || !idx || !dist2) return MVP_EBADARG;
+  if (scratch_short(scratch, scratch_bytes, mvp_knn_scratch_bytes(b, n, m))) return MVP_EBADARG;
   if (b > 65535) return MVP_EBADSHAPE;
   char *sc = reinterpret_cast<char *>(scratch);
   int *fix_cnt = reinterpret_cast<int *>(sc + (size_t)b * (cs_side_bytes(m) + cs_side_bytes(n)));
   int *fix_list = reinterpret_cast<int *>(reinterpret_cast<char *>(fix_cnt) + knn_cnt_bytes(b));
-  if (hipMemsetAsync(fix_cnt, 0, (size_t)knn_cnt_bytes(b), as_stream(stream)) != hipSuccess) return check_launch("mvp_knn_sorted");
-  cs_sort_launch(b, m, n, new_xyz, xyz, sc, as_stream(stream));   // side 0: the queries, side 1: the candidates
-  constexpr int T = 256;
-  const dim3 grid((m + T - 1) / T, b);
+  hipStream_t st = as_stream(stream);
+  if (hipMemsetAsync(fix_cnt, 0, (size_t)knn_cnt_bytes(b), st) != hipSuccess) return check_launch("mvp_knn_sorted");
+  cs_sort_launch(b, m, n, new_xyz, xyz, sc, st);   // side 0: the queries, side 1: the candidates
   if (nsample <= 8)
-    hipLaunchKernelGGL((knn_sorted_kernel<T, 9>), grid, dim3(T), 0, as_stream(stream), n, m, nsample, sc, idx, dist2, fix_cnt, fix_list);
+    knn_sorted_launch<9>(b, n, m, nsample, sc, idx, dist2, fix_cnt, fix_list, st);
   else if (nsample <= 16)
-    hipLaunchKernelGGL((knn_sorted_kernel<T, 17>), grid, dim3(T), 0, as_stream(stream), n, m, nsample, sc, idx, dist2, fix_cnt, fix_list);
+    knn_sorted_launch<17>(b, n, m, nsample, sc, idx, dist2, fix_cnt, fix_list, st);
   else
-    hipLaunchKernelGGL((knn_sorted_kernel<T, 33>), grid, dim3(T), 0, as_stream(stream), n, m, nsample, sc, idx, dist2, fix_cnt, fix_list);
+    knn_sorted_launch<33>(b, n, m, nsample, sc, idx, dist2, fix_cnt, fix_list, st);
   // queries with equal distances among their k + 1 nearest: the reference's own sequence of heap operations
-  hipLaunchKernelGGL(knn_fix_kernel, dim3(16, b), dim3(kFixWaves * 64), 0, as_stream(stream), n, m, nsample, xyz, new_xyz, idx,
-                     dist2, fix_cnt, fix_list);
+  hipLaunchKernelGGL(knn_fix_kernel, dim3(16, b), dim3(kFixWaves * 64), 0, st, n, m, nsample, xyz, new_xyz, idx, dist2,
+                     fix_cnt, fix_list);
   return check_launch("mvp_knn_sorted");
 }
 

@@ -154,6 +154,72 @@ def test_guards_and_scratch_sizes_of_the_widened_entry_points():
     assert lib.mvp_furthest_point_sampling_sorted(1, 0, 4, null, null, null, null, 0, null) == -1
 
 
+def test_return_codes_of_the_sorted_geometry_entry_points():
+    """mvp_knn_sorted, mvp_chamfer_forward_sorted and mvp_furthest_point_sampling_sorted: the scratch and pointer guards
+    of the sorted route, and the edges of the rule that hands a call to the plain entry point.  Every row returns before
+    a launch: a guard refuses, or the batch is empty."""
+    from mvp_benchmark_amd import _lib
+    lib = _lib.load()
+    OK, EBADSHAPE, EBADARG = 0, -1, -2
+    null, dummy, odd = ctypes.c_void_p(0), ctypes.c_void_p(4096), ctypes.c_void_p(4097)
+    # name -> (dimensions of a sorted-route shape, device pointers, scratch size of (b, dims), has a b > 65535 guard)
+    entries = {
+        "mvp_knn_sorted": ((4096, 1024, 8), 4, lambda b, n, m, k: _lib.knn_scratch_bytes(b, n, m), True),
+        "mvp_chamfer_forward_sorted": ((4096, 4096), 6, _lib.chamfer_scratch_bytes, True),
+        "mvp_furthest_point_sampling_sorted": ((4097, 4), 3, lambda b, n, m: _lib.fps_scratch_bytes(b, n), False),
+    }
+
+    def run(name, b, dims, ptrs, scratch, nbytes):
+        nptr = entries[name][1]
+        ptrs = list(ptrs) if isinstance(ptrs, (list, tuple)) else [ptrs] * nptr
+        return getattr(lib, name)(b, *dims, *ptrs, scratch, nbytes, null)
+
+    for name, (dims, nptr, need_of, guards_b) in entries.items():
+        need = need_of(1, *dims)
+        assert need > 0, name
+        assert run(name, 1, dims, dummy, null, need) == EBADARG, name           # no scratch
+        assert run(name, 1, dims, dummy, null, 0) == EBADARG, name
+        assert run(name, 1, dims, dummy, dummy, need - 1) == EBADARG, name      # one byte short
+        assert run(name, 1, dims, dummy, odd, need + 16) == EBADARG, name       # misaligned
+        for missing in range(nptr):                                            # each input / output on its own
+            ptrs = [null if i == missing else dummy for i in range(nptr)]
+            assert run(name, 1, dims, ptrs, dummy, need) == EBADARG, (name, missing)
+        if guards_b:
+            # more clouds than a grid dimension holds, with scratch that passes: the shape is what is wrong ...
+            assert run(name, 65536, dims, dummy, dummy, need_of(65536, *dims)) == EBADSHAPE, name
+            # ... and without scratch the scratch is refused first
+            assert run(name, 65536, dims, dummy, null, 0) == EBADARG, name
+        assert run(name, 0, dims, null, null, 0) == OK, name                    # the empty batch needs nothing
+
+    # One below each threshold of the sorted route the call is the plain entry point's, which wants no scratch: its code,
+    # not EBADARG.  The empty batch returns MVP_OK before a pointer is read; where the plain entry point has a guard the
+    # sorted route answers differently (b = 65536 without scratch: EBADSHAPE there, EBADARG here), that one names the
+    # side of the threshold a shape is on without a launch.
+    below = {
+        "mvp_knn_sorted": [(4095, 1024, 8), (2047, 2048, 8), (4096, 1023, 8), (4096, 1024, 33)],
+        "mvp_chamfer_forward_sorted": [(2047, 16384), (16384, 2047), (4095, 4097)],     # 4095 * 4097 = 2^24 - 1
+        "mvp_furthest_point_sampling_sorted": [(4096, 4), (16385, 4), (4097, 1)],
+    }
+    at = {
+        "mvp_knn_sorted": [(4096, 1024, 8), (2048, 2048, 8), (4096, 1024, 32)],
+        "mvp_chamfer_forward_sorted": [(2048, 8192), (8192, 2048), (4096, 4096)],
+        "mvp_furthest_point_sampling_sorted": [(4097, 4), (16384, 2)],
+    }
+    for name, (_, _, _, guards_b) in entries.items():
+        for dims in below[name]:
+            assert run(name, 0, dims, dummy, null, 0) == OK, (name, dims)
+            if guards_b:
+                assert run(name, 65536, dims, dummy, null, 0) == EBADSHAPE, (name, dims)
+        for dims in at[name]:
+            assert run(name, 1, dims, dummy, null, 0) == EBADARG, (name, dims)
+            if guards_b:
+                assert run(name, 65536, dims, dummy, null, 0) == EBADARG, (name, dims)
+    # the plain entry points' own shape guards come through the fall-back
+    assert run("mvp_knn_sorted", 1, (4096, 1024, 101), dummy, null, 0) == EBADSHAPE
+    assert run("mvp_chamfer_forward_sorted", 1, (0, 4096), dummy, null, 0) == EBADSHAPE
+    assert run("mvp_furthest_point_sampling_sorted", 1, (0, 4), dummy, null, 0) == EBADSHAPE
+
+
 def test_return_codes_of_the_gather_and_scatter_entry_points():
     """The nine entry points of csrc/pn2_gather.hip that share one body: which guard answers, and in which order.  Every
     row returns before a launch (null pointers, or dummy ones behind a guard that refuses first).  Dimensions are given
