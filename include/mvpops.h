@@ -660,12 +660,17 @@ int mvp_pointwise_wgrad_mfma_ex(int b, int cin, int cout, int len, const float *
  *   gw[co][ci]   = sum_b g[b][co] x[b][ci][idx[b][co]],   gb[co] = sum_b g[b][co]
  *   gx[b][ci][l] = sum_{co : idx[b][co] = l} g[b][co] w[co][ci]     (0 elsewhere; every entry written)
  * x (b,cin,len), w (cout,cin), g (b,cout) = the gradient of v, idx (b,cout) int32 = the position
- * torch.max reported.  gx, gw may each be NULL (that gradient is not needed), gb too.
- * len <= 16384, cout <= 4096.  Fixed summation orders: bit-reproducible.  scratch (may be NULL):
- * mvp_pointwise_max_backward_scratch_bytes(...) bytes (0 = shape not covered by the staged pass) in which the
- * weight gradient stages the b * cout winning columns of x with coalesced accesses; without it the columns are
- * gathered directly (a 64-byte sector per value).  The reference lets cuDNN run its dense data- and
- * weight-gradient passes on the max's gradient, a tensor of zeros. */
+ * torch.max reported.  gx, gw may each be NULL (that gradient is not needed), gb too: each one that is given
+ * is written, whichever others are (x is read for gw only, w for gx only).
+ * len <= 16384, cout <= 4096, b <= 65535; gx needs (3 cout + len) * 4 <= 30000 (the sort of a cloud's winners
+ * lives in LDS).  Fixed summation orders: bit-reproducible.  scratch (may be NULL):
+ * mvp_pointwise_max_backward_scratch_bytes(...) bytes (0 = shape not covered by the staged pass: the same
+ * LDS limit), contents irrelevant.  gw by one of two routes: with scratch of at least that size (and > 0) the
+ * b * cout winning columns of x are staged there with coalesced accesses and then added; with scratch NULL,
+ * too small, or a shape the staged pass does not cover, the columns are gathered directly (a 64-byte sector per
+ * value).  Both add g[b][co] * column over the clouds in ascending order in one fmaf chain: the same bits.
+ * gb is the plain sum of g over the clouds in ascending order, with or without gw.  The reference lets cuDNN
+ * run its dense data- and weight-gradient passes on the max's gradient, a tensor of zeros. */
 long long mvp_pointwise_max_backward_scratch_bytes(int b, int cin, int cout, int len);
 int mvp_pointwise_max_backward(int b, int cin, int cout, int len, const float *x,
                                const float *w, const float *g, const int *idx,

@@ -266,6 +266,17 @@ __global__ __launch_bounds__(kMxThreads) void convmax_wgrad_reduce_kernel(int b,
   }
 }
 
+// gb without gw: a thread per output channel adds g over the clouds in order -- the sum, and the bits, that the two
+// weight-gradient kernels above write beside gw.
+__global__ __launch_bounds__(kMxThreads) void convmax_bias_kernel(int b, int cout, const float *__restrict__ g,
+                                                                 float *__restrict__ gb) {
+  const int co = blockIdx.x * kMxThreads + threadIdx.x;
+  if (co >= cout) return;
+  float s = 0.f;
+  for (int c = 0; c < b; ++c) s += g[(size_t)c * cout + co];
+  gb[co] = s;
+}
+
 }  // namespace mvp
 
 using namespace mvp;
@@ -297,6 +308,8 @@ extern "C" int mvp_pointwise_max_backward(int b, int cin, int cout, int len, con
     } else {
       hipLaunchKernelGGL(convmax_wgrad_kernel, dim3(cout), dim3(kMxThreads), 0, st, b, cin, cout, len, x, g, idx, gw, gb);
     }
+  } else if (gb) {
+    hipLaunchKernelGGL(convmax_bias_kernel, dim3((cout + kMxThreads - 1) / kMxThreads), dim3(kMxThreads), 0, st, b, cout, g, gb);
   }
   if (gx) {
     const size_t lds = (size_t)(cout_p2 + cout + len) * 4;

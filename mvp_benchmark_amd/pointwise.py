@@ -600,7 +600,7 @@ class _PointwiseConvMax(Function):
         gx = gw = gb = None
         if _plan_max_backward(_describe(x3, w2)) == "sparse":
             gx = torch.empty_like(x3) if need_x else None
-            gw = torch.empty_like(w2) if (need_w or need_b) else None
+            gw = torch.empty_like(w2) if need_w else None
             gb = torch.empty(cout, dtype=torch.float32, device=x.device) if need_b else None
             nbytes = pointwise_max_backward_scratch_bytes(B, cin, cout, length) if gw is not None else 0
             scratch = _wgrad_scratch(x.device, nbytes) if nbytes else None     # the winning columns of x, staged
