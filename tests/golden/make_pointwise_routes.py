@@ -37,7 +37,8 @@ DEV = "cuda:0"
 
 DEFAULTS = dict(USE_MFMA=True, MFMA_TRAIN=True, MFMA_DGRAD=True, MFMA_WGRAD_MIN_CIN=1, MFMA_WGRAD_MIN_POSITIONS=16384,
                 MFMA_MIN_CH=1, MFMA_SKINNY_FWD_MAX_CIN=136, LIBRARY_IS_GEMM=False)
-CASE_DEFAULTS = dict(x="dense", w="dense", go="dense", bias=True, flags={}, grad="", sel={}, cout2=0, fix="", boundary="")
+CASE_DEFAULTS = dict(x="dense", w="dense", go="dense", bias=True, flags={}, grad="", sel={}, cout2=0, fix="", boundary="",
+                     res="dense", cb="dense")      # (res / cb: the layouts of the residual and of cloud_bias -- no recorded row sets them)
 WATCH = {"aten::convolution": "conv", "aten::convolution_backward": "conv_backward", "aten::bmm": "gemm",
          "aten::baddbmm": "gemm", "aten::mm": "gemm", "aten::matmul": "gemm", "aten::einsum": "einsum",
          "aten::threshold_backward": "threshold_backward"}
@@ -247,35 +248,48 @@ def collect_model_layers():
 
 
 # ---- running a case ------------------------------------------------------------------------------------------------------------
-def _tensor(shape, view, g):
-    """float32 CUDA tensor of `shape`: dense, one float into its storage, or a permuted (channels-last) view."""
+def _draw(size, family, g):
+    """The values of a tensor: randn (family None: what the fixture was recorded on), or a family of
+    tests/conv_gradient_cases.py ("exact": integers in [-4, 4], "random": randn)."""
+    if family is None:
+        return torch.randn(size, generator=g)
+    if os.path.dirname(HERE) not in sys.path:
+        sys.path.insert(0, os.path.dirname(HERE))
+    from conv_gradient_cases import values
+    return values(tuple(size), family, g)
+
+
+def _tensor(shape, view, g, family=None, device=DEV):
+    """float32 tensor of `shape` on `device`: dense, one float into its storage, or a permuted (channels-last; 2-d:
+    transposed) view."""
     n = 1
     for s in shape:
         n *= s
     if view == "offset":
-        return torch.randn(n + 1, generator=g).to(DEV)[1:].view(shape)
+        return _draw((n + 1,), family, g).to(device)[1:].view(shape)
     if view == "permuted":
         perm = (0,) + tuple(range(2, len(shape))) + (1,) if len(shape) > 2 else (1, 0)
         inv = [perm.index(i) for i in range(len(shape))]
-        return torch.randn([shape[p] for p in perm], generator=g).to(DEV).permute(inv)
-    return torch.randn(shape, generator=g).to(DEV)
+        return _draw([shape[p] for p in perm], family, g).to(device).permute(inv)
+    return _draw(shape, family, g).to(device)
 
 
-def build_inputs(c, seed=0):
+def build_inputs(c, seed=0, family=None, device=DEV):
     """The tensors of a case: dict with x, w, b, w2, res, cb (None where absent), requires_grad set from c["grad"]."""
     c = full(c)
     g = torch.Generator().manual_seed(seed)
     B, cin, cout, tail = c["B"], c["cin"], c["cout"], tuple(c["tail"])
     ones = (1,) * len(tail)
-    t = dict(x=_tensor((B, cin) + tail, c["x"], g), w=_tensor((cout, cin) + ones, c["w"], g), b=None, w2=None, res=None, cb=None)
+    t = dict(x=_tensor((B, cin) + tail, c["x"], g, family, device), w=_tensor((cout, cin) + ones, c["w"], g, family, device),
+             b=None, w2=None, res=None, cb=None)
     if c["bias"]:
-        t["b"] = torch.randn(cout, generator=g).to(DEV)
+        t["b"] = _draw((cout,), family, g).to(device)
     if c["cout2"]:
-        t["w2"] = torch.randn((c["cout2"], cin) + ones, generator=g).to(DEV)
+        t["w2"] = _draw((c["cout2"], cin) + ones, family, g).to(device)
     if c["flags"].get("residual"):
-        t["res"] = torch.randn((B, cout) + tail, generator=g).to(DEV)
+        t["res"] = _tensor((B, cout) + tail, c["res"], g, family, device)
     if c["flags"].get("cloud_bias"):
-        t["cb"] = torch.randn(B, cout, generator=g).to(DEV)
+        t["cb"] = _tensor((B, cout), c["cb"], g, family, device)
     for letter, name in (("x", "x"), ("w", "w"), ("b", "b"), ("r", "res"), ("c", "cb")):
         if letter in c["grad"] and t[name] is not None:
             t[name].requires_grad_()
@@ -298,9 +312,14 @@ def call_entry(pw, c, t):
     return (pw.pointwise_conv_max(t["x"], t["w"], t["b"]),)
 
 
-def grad_outs(c, outs, seed=1):
+def grad_outs(c, outs, seed=1, family=None):
     g = torch.Generator().manual_seed(seed)
-    return [_tensor(tuple(o.shape), full(c)["go"], g) for o in outs]
+    return [_tensor(tuple(o.shape), full(c)["go"], g, family, o.device) for o in outs]
+
+
+def grad_inputs(t):
+    """[(name, tensor)] of the tensors of build_inputs that require a gradient, in the order run_case returns theirs."""
+    return [(k, v) for k, v in t.items() if v is not None and v.requires_grad]
 
 
 def _graph_convs(outs):
@@ -317,8 +336,12 @@ def _graph_convs(outs):
     return sorted(names)
 
 
-def run_case(c, tensors=None):
-    """-> (trace, outputs, gradients): the case run under its selectors with `call` wrapped and the operator profiler on."""
+def run_case(c, tensors=None, grad_out=None, profiled=True):
+    """-> (trace, outputs, gradients): the case run under its selectors with `call` wrapped and the operator profiler on
+    (profiled=False: without it, trace["ops"] stays empty).  gradients: one per entry of grad_inputs(tensors), in that
+    order, for grad_out (default: grad_outs(c, outputs)); None where the graph gave that input none -- the trace does not
+    care, the value tests assert on it."""
+    import contextlib
     import mvp_benchmark_amd.pointwise as pw
     from mvp_benchmark_amd._lib import MvpOpsError
     from torch.profiler import ProfilerActivity, profile
@@ -337,20 +360,22 @@ def run_case(c, tensors=None):
     pw.call = traced
     try:
         t = tensors or build_inputs(c)
-        inputs = [v for v in t.values() if v is not None and v.requires_grad]
-        with profile(activities=[ProfilerActivity.CPU]) as prof:
+        inputs = [v for _, v in grad_inputs(t)]
+        with (profile(activities=[ProfilerActivity.CPU]) if profiled else contextlib.nullcontext()) as prof:
             try:
                 with torch.enable_grad():
                     outs = call_entry(pw, c, t)
                     trace["fn"] = _graph_convs(outs)
                     if inputs:
-                        grads = torch.autograd.grad(outs, inputs, grad_outs(c, outs), allow_unused=True)
+                        grads = torch.autograd.grad(outs, inputs, grad_out or grad_outs(c, outs), allow_unused=True)
             except MvpOpsError as exc:         # a host-side refusal of the arguments (nothing was launched); anything else,
                 if "HIP" in str(exc):          # a HIP error included, ends the run
                     raise
                 trace["error"] = type(exc).__name__
-            torch.cuda.synchronize()
-        trace["ops"] = sorted({WATCH[e.key] for e in prof.key_averages() if e.key in WATCH})
+            if t["x"].is_cuda:
+                torch.cuda.synchronize()
+        if profiled:
+            trace["ops"] = sorted({WATCH[e.key] for e in prof.key_averages() if e.key in WATCH})
     finally:
         pw.call = orig_call
         for k, v in saved.items():

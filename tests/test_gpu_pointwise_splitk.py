@@ -257,6 +257,54 @@ def test_non_finite_values_go_where_the_unsplit_kernel_sends_them():
     assert same(y, epilogue(chunk_sum(x, t["w"], k_chunk, kmajor), t["bias"], residual=res, res_is_mask=True))
 
 
+UNALIGNED = (2, 515, 40, 68, 128, False)     # a 515-long reduction in chunks of 128: four whole ones and one of 3
+
+
+@pytest.mark.parametrize("flags,with_residual", [(0, False), (2, True), (4, True)], ids=["plain", "residual_relu_after", "residual_mask"])
+def test_unaligned_y_and_residual_take_the_reduce_kernels_scalar_branch(flags, with_residual):
+    """y and / or the residual a view one float into its storage (4 bytes past a 16-byte boundary): the reduce kernel loads
+    and stores them one float at a time (vec_io = 0).  The bits are those of the aligned call (themselves the chunk sum and
+    the torch epilogue), and the float before and the float after the view of y keep what they held."""
+    from mvp_benchmark_amd import _lib
+    b, cin, cout, length, k_chunk, kmajor = UNALIGNED
+    t = inputs(UNALIGNED)
+    n = b * cout * length
+    nbytes = _lib.pointwise_mfma_splitk_scratch_bytes(b, cin, cout, length, k_chunk)
+    assert nbytes == 5 * n * 4
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+    guard = 12345.5
+
+    def view_one_float_in(values=None):
+        buf = torch.full((n + 2,), guard, device=DEV)
+        if values is not None:
+            buf[1:n + 1] = values.flatten()
+        v = buf[1:n + 1].view(b, cout, length)
+        assert v.data_ptr() % 16 == 4 and v.is_contiguous()
+        return buf, v
+
+    def call(y, residual):
+        _lib.call(SPLITK, DEV, b, cin, cout, length, t["x"], None, t["w"], 0, 0, t["bias"], 0, residual, flags, y, k_chunk,
+                  scratch, nbytes)
+
+    aligned_res = t["residual"] if with_residual else None
+    assert aligned_res is None or aligned_res.data_ptr() % 16 == 0
+    want = torch.full((b, cout, length), guard, device=DEV)
+    assert want.data_ptr() % 16 == 0
+    call(want, aligned_res)
+    assert torch.equal(want, epilogue(chunk_sum(t["x"], t["w"], k_chunk, kmajor), t["bias"], residual=aligned_res,
+                                      res_is_mask=bool(flags & 4), relu_after=bool(flags & 2)))
+    placements = [(True, False)] + ([(False, True), (True, True)] if with_residual else [])
+    for y_off, res_off in placements:
+        buf, y = view_one_float_in() if y_off else (None, torch.full((b, cout, length), guard, device=DEV))
+        res = aligned_res
+        if res_off:
+            _, res = view_one_float_in(aligned_res)
+        call(y, res)
+        assert torch.equal(y, want), (y_off, res_off, int((y != want).sum()))
+        if y_off:
+            assert buf[0].item() == guard and buf[n + 1].item() == guard
+
+
 # ------------------------------------------------------------------------------------------------ through autograd
 _spec = importlib.util.spec_from_file_location("make_pointwise_routes", os.path.join(HERE, "golden", "make_pointwise_routes.py"))
 rec = importlib.util.module_from_spec(_spec)
