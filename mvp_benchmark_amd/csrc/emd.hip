@@ -71,11 +71,6 @@
 
 namespace mvp {
 
-// emd_lean.hip: the kernel that runs the one-bidder-per-wave rounds after the hand-over
-hipError_t emd_lean_launch(int b, int n, int w, const float *xyz1, float *dist, int *assignment, float eps,
-                           int iters, char *scratch, int fast_ok, int plan_round, int plan_every,
-                           unsigned long long plan_widths, int res_cap, hipStream_t stream);
-
 template <int W>
 __global__ __launch_bounds__(kEmdThreads) void emd_auction_kernel(
     int b, int bpad, int n, const float *__restrict__ xyz1, const float *__restrict__ xyz2,
@@ -994,29 +989,14 @@ __global__ __launch_bounds__(256) void emd_grad_kernel(
   grad_xyz[a + 2] += g * (xyz1[a + 2] - xyz2[c + 2]);
 }
 
-// Tuning / A-B knobs of the auction.  Process-wide; compiled-in defaults, mvp_emd_configure() changes them at run time
-// (cluster, same_xcd, split, resident_cap).  The release library reads NOTHING from the environment; a build with
-// -DMVP_TEST_HOOKS (`make hooks` -> libmvpops_hooks.so, loaded by the tests / tools that need it) also takes, ONCE at first use,
+// Tuning / A-B knobs of the auction: EmdKnobs, their compiled-in defaults and what each `split` level launches are
+// emd_plan.h's.  Process-wide; mvp_emd_configure() changes them at run time (cluster, same_xcd, split, resident_cap).
+// The release library reads NOTHING from the environment; a build with -DMVP_TEST_HOOKS (`make hooks` ->
+// libmvpops_hooks.so, loaded by the tests / tools that need it) also takes, ONCE at first use,
 //   MVP_EMD_CLUSTER / MVP_EMD_SAME_XCD / MVP_EMD_SPLIT / MVP_EMD_RESIDENT_CAP   the same four knobs
-//   MVP_EMD_PLAN_ROUND / MVP_EMD_PLAN_EVERY / MVP_EMD_PLAN_WIDTHS               the tiered launch's plan (emd_lean.hip)
+//   MVP_EMD_PLAN_ROUND / MVP_EMD_PLAN_EVERY / MVP_EMD_PLAN_WIDTHS               the tiered launches' plan
 //   MVP_EMD_TIERS_FAIL                                                          "the tiered kernel does not fit this device"
 //   MVP_EMD_POLL_DISTRUST                                                       gathered-bid rounds of odd count re-read their bid records (emd_lean_round_gathered.inc)
-// split: 0 one kernel runs every round; 1: the rounds after the last four-bidders-per-wave round run in the lean kernel
-// (emd_lean.hip); 2: + cluster widths dealt out by load at round 300 (33..64 clouds of >= 4096 points); 3: + clouds of
-// <= 4096 points finish LDS-resident on one workgroup, in a launch of their own (emd_resident.hip); 4: ... inside the lean
-// launch, on member 0 of the cloud's cluster; 5 (default): + gathered-bid rounds.
-// The results do not depend on any of them (bit-identical; tests/test_gpu_ops.py).
-struct EmdKnobs {
-  int cluster, same_xcd, split;   // split: 0 one kernel, 1 + the lean kernel, 2 + planned cluster widths (emd_lean.hip), 3 + resident tail (own launch), 4 fused into the lean launch, 5 + gathered-bid rounds
-  int plan_round, plan_every;     // split == 2: round of the first plan; rounds per planned launch
-  unsigned long long plan_widths; // widths of an XCD's 8 cloud slots, heaviest first, 4 bits each
-  int res_cap;                    // split == 3: unassigned persons at which a cloud of <= 4096 points moves into LDS (emd_resident.hip)
-  int poll_distrust;              // MVP_TEST_HOOKS only: bit 2 of the lean launch's fast_ok
-};
-// The compiled-in defaults: of the process-wide knobs and of every mvp_emd_forward_plan call.
-static EmdKnobs emd_default_knobs() {
-  return EmdKnobs{kMaxCluster, 1, 5, 300, 4096, 0ull, 16, 0};   // plan_widths 0: from the loads (MVP_EMD_PLAN_WIDTHS=8,5,4,4,3,3,3,2 fixes them)
-}
 // The four public fields (mvp_emd_configure's arguments, MvpEmdPlan's members) into `k`: negative = keep.  All four are
 // checked before anything is written, so a rejected call changes nothing.
 static int emd_apply_knobs(EmdKnobs &k, int cluster, int same_xcd, int split, int resident_cap) {
@@ -1061,33 +1041,18 @@ static EmdKnobs emd_knobs() {
   return emd_knobs_locked();
 }
 
-// Workgroups per cloud: as many (1, 2, 4, 8) as keep b*W workgroups co-resident,
-// one per CU.  MVP_EMD_CLUSTER=1|2|4|8 overrides (still capped by the CU count).
-static int emd_cluster_width(int b, int want) {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return 1;
-  int w = 1;
-  while (w * 2 <= want && w * 2 <= kMaxCluster && (long long)b * w * 2 <= cus) w *= 2;
-  return w;
-}
-
-template <int W>
-static hipError_t emd_launch(int b, int n, const float *xyz1, const float *xyz2, float *dist,
-                             int *assignment, float eps, int iters, char *scratch, int lean, int fast_ok,
-                             hipStream_t stream) {
-  int bpad = W == 1 ? b : (b + 7) / 8 * 8;
-  if (W == 1) {
-    hipLaunchKernelGGL(emd_auction_kernel<1>, dim3(b), dim3(kEmdThreads), 0, stream, b, bpad, n,
-                       xyz1, xyz2, dist, assignment, eps, iters, scratch, 0, lean);
-    return hipSuccess;
+// A step of the first kernel on its cluster width.
+hipError_t emd_first_launch(const EmdStep &s, EmdCall c) {
+  int bpad = emd_bpad(c.b, s.W), fast_ok = s.fast_ok, lean = s.lean;
+  void *args[] = {&c.b, &bpad, &c.n, &c.xyz1, &c.xyz2, &c.dist, &c.assignment, &c.eps, &c.iters, &c.scratch, &fast_ok, &lean};
+  const void *kernel = nullptr;   // (no such instantiation: the launch fails)
+  switch (s.W) {
+    case 8: kernel = reinterpret_cast<const void *>(emd_auction_kernel<8>); break;
+    case 4: kernel = reinterpret_cast<const void *>(emd_auction_kernel<4>); break;
+    case 2: kernel = reinterpret_cast<const void *>(emd_auction_kernel<2>); break;
+    case 1: kernel = reinterpret_cast<const void *>(emd_auction_kernel<1>); break;
   }
-  // cluster members wait for each other: the launch must be checked against
-  // the device's residency (cooperative launch does exactly that)
-  void *args[] = {&b, &bpad, &n, &xyz1, &xyz2, &dist, &assignment, &eps, &iters, &scratch, &fast_ok, &lean};
-  return hipLaunchCooperativeKernel(reinterpret_cast<const void *>(emd_auction_kernel<W>),
-                                    dim3(W * bpad), dim3(kEmdThreads), args, 0, stream);
+  return emd_launch_step(kernel, s, args, c.stream);
 }
 
 }  // namespace mvp
@@ -1124,24 +1089,24 @@ static int emd_forward_with(const EmdKnobs &knobs, int b, int n, const float *xy
   // barrier granules, hand-over records and statistics start from zero on every call
   if (hipMemsetAsync(sbase + (size_t)b * emd_scratch_per_cloud(n), 0, (size_t)b * kEmdTailPerCloud, st) != hipSuccess)
     return check_launch("mvp_emd_forward");
-  int w = emd_cluster_width(b, knobs.cluster);
-  // Two launches when the auction is long enough to have a tail: the first kernel hands a cloud
-  // over when at least `lean` rounds are left (0: never); the second exits at once for clouds
-  // that were not handed over.
-  const int lean = knobs.split && iters > kLeanMinRounds ? kLeanMinRounds : 0;
-  hipError_t err = hipErrorUnknown;
-  if (w == 8) err = emd_launch<8>(b, n, xyz1, xyz2, dist, assignment, eps, iters, sbase, lean, knobs.same_xcd, st);
-  else if (w == 4) err = emd_launch<4>(b, n, xyz1, xyz2, dist, assignment, eps, iters, sbase, lean, knobs.same_xcd, st);
-  else if (w == 2) err = emd_launch<2>(b, n, xyz1, xyz2, dist, assignment, eps, iters, sbase, lean, knobs.same_xcd, st);
-  if (err != hipSuccess) {  // w == 1, or the cluster does not fit this device
-    (void)hipGetLastError();
-    w = 1;
-    (void)emd_launch<1>(b, n, xyz1, xyz2, dist, assignment, eps, iters, sbase, lean, 0, st);
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
+#ifdef MVP_TEST_HOOKS
+  static const bool tiers_fail = getenv("MVP_EMD_TIERS_FAIL") != nullptr;   // (libmvpops_hooks.so only: behave as if it did not fit)
+#else
+  constexpr bool tiers_fail = false;
+#endif
+  // The launches of the call, in emd_plan.h's order; a refused launch (the cooperative grid does not fit this device)
+  // goes back to the plan, which answers it or ends.
+  const EmdCall call{b, n, xyz1, xyz2, dist, assignment, eps, iters, sbase, st};
+  EmdPlan plan{knobs, b, n, iters, cus};
+  hipError_t (*const kLaunch[])(const EmdStep &, EmdCall) = {emd_first_launch, emd_lean_launch, emd_lean_launch, emd_resident_launch};   // by EmdKernel
+  EmdStep s;
+  for (bool ok = true; emd_plan_next(plan, ok, s);) {
+    // (tiers_fail: a tiered step counts as refused)
+    ok = !(s.kernel == kEmdTiers && tiers_fail) && kLaunch[s.kernel](s, call) == hipSuccess;
+    if (!ok && s.refusable) (void)hipGetLastError();
   }
-  if (lean && emd_lean_launch(b, n, w, xyz1, dist, assignment, eps, iters, sbase, knobs.same_xcd | (knobs.split >= 5 ? 2 : 0) | (knobs.poll_distrust ? 4 : 0),
-                              knobs.plan_round, knobs.split >= 2 ? knobs.plan_every : 0, knobs.plan_widths,
-                              knobs.split >= 4 ? knobs.res_cap : knobs.split == 3 ? -knobs.res_cap : 0, st) != hipSuccess)
-    return check_launch("mvp_emd_forward");
   return check_launch("mvp_emd_forward");
 }
 

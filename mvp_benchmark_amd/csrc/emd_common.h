@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "emd_plan.h"
 
 namespace mvp {
 
@@ -20,7 +21,6 @@ constexpr int kRecCap = 512;     // list positions whose person record is cached
 #endif
 constexpr int kRowModeMin = MVP_EMD_ROWMIN;  // bidders per round above which 4 bidders share a wave
 constexpr int kRowListCap = 128; // per-row (bidder) list of surviving leaves, flushed when full
-constexpr int kMaxCluster = 8;   // workgroups per cloud (W)
 constexpr int kChgCap = 2048;    // refreshed price bounds a workgroup can broadcast per round
 #ifndef MVP_EMD_SOLO
 #define MVP_EMD_SOLO 16
@@ -39,7 +39,8 @@ constexpr int kFewMax = kFewPos * kEmdWaves;
 constexpr unsigned kSpinLimit = 1u << 24;  // bound of every cluster wait (tens of seconds), then abort
 // The lean kernel (emd_lean.hip) takes a cloud over once no workgroup has more than kRowModeMin
 // bidders, at most kLeanCap persons are unassigned (their number never grows, so every later
-// list fits the LDS record cache) and at least kLeanMinRounds rounds are left.
+// list fits the LDS record cache) and at least kLeanMinRounds rounds are left (kLeanMinRounds, kMaxCluster, kResMaxN,
+// kResList: emd_plan.h, which the host's launch plan reads too).
 // Re-tuned with the leaf index (round 6, same-box sweep of six builds, profiles/r6c_emd_handover_sweep.txt): the one-bidder-
 // per-wave searches got 14 % cheaper and the four-per-wave ones 14 % dearer, so the lean kernel takes over EARLIER --
 // kRowModeMin x kLeanCap = 96 x 384 (rounds 2-5: "64..160 x 384 / 512 all within 0.2 ms") -> 192 x 512 (the record cache's
@@ -48,7 +49,6 @@ constexpr unsigned kSpinLimit = 1u << 24;  // bound of every cluster wait (tens 
 #define MVP_EMD_LEANCAP 512
 #endif
 constexpr int kLeanCap = MVP_EMD_LEANCAP;
-constexpr int kLeanMinRounds = 64;
 static_assert(kLeanCap <= kRecCap, "the lean kernel keeps every list entry's record in LDS");
 // The resident kernel (emd_resident.hip) takes a cloud of at most kResMaxN points over once at most
 // `res_cap` <= kResList persons are unassigned and at least kResMinRounds rounds are left: the whole
@@ -60,8 +60,6 @@ constexpr int kGCap = 256;      // bids of a cloud per round
 constexpr int kGMaxN = 16384;   // 14-bit slots / person indices in a granule
 constexpr int kGStride = 2 * kGCap + 8;   // 8-byte words of one parity's bid area: the bids, then a heartbeat per member
 constexpr size_t kEmdBidBytes = 2 * (size_t)kGStride * 8;   // per cloud, both parities
-constexpr int kResMaxN = 4096;
-constexpr int kResList = 64;
 constexpr int kResMinRounds = 32;
 
 // Filter slack.  An object is skipped only if
@@ -136,6 +134,28 @@ __host__ __device__ inline EmdHandover *emd_handover(char *tail, int b, int clou
 }
 __host__ __device__ inline long long *emd_stats(char *tail, int b, int cloud) {
   return reinterpret_cast<long long *>(tail + (size_t)b * (256 * kEmdGranuleSets + kEmdBidBytes + sizeof(EmdHandover))) + 2 * (size_t)cloud;
+}
+
+// Host side.  What every launch of one mvp_emd_forward call shares, and the launchers of a planned step (emd_plan.h),
+// one per kernel family: the only places where a step's (W, resn) becomes a template instantiation and where a kernel's
+// argument array is packed.
+struct EmdCall {
+  int b, n;
+  const float *xyz1, *xyz2;
+  float *dist;
+  int *assignment;
+  float eps;
+  int iters;
+  char *scratch;   // (the per-cloud areas' start: the END of the caller's buffer)
+  hipStream_t stream;
+};
+hipError_t emd_first_launch(const EmdStep &s, EmdCall c);      // emd.hip: kEmdFirst
+hipError_t emd_lean_launch(const EmdStep &s, EmdCall c);       // emd_lean.hip: kEmdLean, kEmdTiers
+hipError_t emd_resident_launch(const EmdStep &s, EmdCall c);   // emd_resident.hip: kEmdResident
+inline hipError_t emd_launch_step(const void *kernel, const EmdStep &s, void **args, hipStream_t stream) {
+  // (cluster members wait for each other: a cooperative launch checks the grid against the device's residency)
+  return s.coop ? hipLaunchCooperativeKernel(kernel, dim3(s.grid), dim3(kEmdThreads), args, 0, stream)
+                : hipLaunchKernel(kernel, dim3(s.grid), dim3(kEmdThreads), args, 0, stream);
 }
 
 __device__ __forceinline__ EmdScratch emd_carve(char *base, int n) {

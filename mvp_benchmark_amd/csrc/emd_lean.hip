@@ -25,7 +25,6 @@
 // The accessors of the shared auction state (sa.ld_obj, sa.st_ostate, ...) are EmdShared<W> of emd_common.h, the same as
 // emd_auction_kernel's; the probes of the instrumented builds (EMD_PROF, EMD_CTIME, GMT) are emd_probe.h's and expand to
 // nothing in the release build.
-#include <cstdlib>
 #include <type_traits>
 
 #include "emd_common.h"
@@ -36,10 +35,6 @@
 namespace mvp {
 
 constexpr int kLeanBid = 512;
-
-// emd_resident.hip
-hipError_t emd_resident_launch(int b, int n, float *dist, int *assignment, float eps, int iters, char *scratch,
-                               hipStream_t stream);
 
 // The kernels' LDS, one object per kernel: the tiers kernel holds the round loop three times (one
 // instance per cluster width), all on the same memory.
@@ -220,7 +215,7 @@ __device__ __forceinline__ int emd_lean_body(LeanShared &sh, const int cloud, co
   // Gathered-bid rounds (entered below once at most kGCap persons are unassigned; their number never grows): `eg`
   // counts them (tags of the bid granules), `goff` = this member's first position in the cloud-wide order of bids.
   bool gm_now = false;
-  const bool gm_ok = WB != 1 && n <= kGMaxN && (fast_ok & 2) != 0;   // (fast_ok: bit 0 = same-XCD stores, bit 1 = gathered-bid rounds, bit 2 = the MVP_TEST_HOOKS build's MVP_EMD_POLL_DISTRUST)
+  const bool gm_ok = WB != 1 && n <= kGMaxN && (fast_ok & 2) != 0;   // (fast_ok's bits: kFastSameXcd, kFastGathered, kFastPollDistrust of emd_plan.h)
   unsigned eg = (unsigned)resume->epoch_g;
   int goff = 0, gi = 0;
   int gU = 0;   // this member's bidders of the coming gathered-bid round (with goff: derived where the lists are counted)
@@ -562,99 +557,25 @@ __global__ __launch_bounds__(kEmdThreads) void emd_lean_tiers_kernel(
 #undef MVP_LEAN_BODY
 }
 
-template <int WT, int RESN = 0>
-static hipError_t emd_lean_launch_w(int b, int n, const float *xyz1, float *dist, int *assignment, float eps,
-                                    int iters, char *scratch, int fast_ok, int it_stop, int which,
-                                    hipStream_t stream, int u_stop = 0) {
-  int bpad = WT == 1 ? b : (b + 7) / 8 * 8;
-  if (WT == 1) {
-    hipLaunchKernelGGL((emd_lean_kernel<1, RESN>), dim3(b), dim3(kEmdThreads), 0, stream, b, bpad, n, xyz1, dist,
-                       assignment, eps, iters, scratch, 0, it_stop, which, u_stop);
-    return hipSuccess;
+// A step of the rounds the first kernel handed over (clouds that were not handed over exit at once): the lean kernel
+// on one cluster width, or the tiered kernel (the same arguments but the last: the widths' pattern for u_stop).
+hipError_t emd_lean_launch(const EmdStep &s, EmdCall c) {
+  int bpad = emd_bpad(c.b, s.W), fast_ok = s.fast_ok, it_stop = s.it_stop, which = s.which, u_stop = s.u_stop;
+  unsigned long long pattern = s.pattern;
+  const bool tiers = s.kernel == kEmdTiers;
+  void *args[] = {&c.b, &bpad, &c.n, &c.xyz1, &c.dist, &c.assignment, &c.eps, &c.iters, &c.scratch, &fast_ok, &it_stop, &which,
+                  tiers ? (void *)&pattern : (void *)&u_stop};
+  const void *kernel = nullptr;   // (no such instantiation: the launch fails)
+#define MVP_LEAN_KERNEL(W_, R_) case W_ * 8192 + R_: kernel = reinterpret_cast<const void *>(emd_lean_kernel<W_, R_>); break
+  switch (tiers ? -1 : s.W * 8192 + s.resn) {
+    case -1: kernel = reinterpret_cast<const void *>(emd_lean_tiers_kernel); break;
+    MVP_LEAN_KERNEL(8, 0); MVP_LEAN_KERNEL(8, 2048); MVP_LEAN_KERNEL(8, 4096);
+    MVP_LEAN_KERNEL(4, 0); MVP_LEAN_KERNEL(4, 2048); MVP_LEAN_KERNEL(4, 4096);
+    MVP_LEAN_KERNEL(2, 0); MVP_LEAN_KERNEL(2, 2048); MVP_LEAN_KERNEL(2, 4096);
+    MVP_LEAN_KERNEL(1, 0); MVP_LEAN_KERNEL(1, 2048); MVP_LEAN_KERNEL(1, 4096);
   }
-  void *args[] = {&b, &bpad, &n, &xyz1, &dist, &assignment, &eps, &iters, &scratch, &fast_ok, &it_stop, &which, &u_stop};
-  return hipLaunchCooperativeKernel(reinterpret_cast<const void *>(emd_lean_kernel<WT, RESN>), dim3(WT * bpad),
-                                    dim3(kEmdThreads), args, 0, stream);
-}
-
-template <int RESN>
-static hipError_t emd_lean_launch_res(int b, int n, int w, const float *xyz1, float *dist, int *assignment, float eps,
-                                      int iters, char *scratch, int fast_ok, hipStream_t stream, int u_stop) {
-  if (w == 8) return emd_lean_launch_w<8, RESN>(b, n, xyz1, dist, assignment, eps, iters, scratch, fast_ok, iters, 1, stream, u_stop);
-  if (w == 4) return emd_lean_launch_w<4, RESN>(b, n, xyz1, dist, assignment, eps, iters, scratch, fast_ok, iters, 1, stream, u_stop);
-  if (w == 2) return emd_lean_launch_w<2, RESN>(b, n, xyz1, dist, assignment, eps, iters, scratch, fast_ok, iters, 1, stream, u_stop);
-  return emd_lean_launch_w<1, RESN>(b, n, xyz1, dist, assignment, eps, iters, scratch, fast_ok, iters, 1, stream, u_stop);
-}
-
-// Runs the rounds the first kernel handed over.  Clouds that were not handed over exit at once.
-// plan_every = 0: one launch with the cluster width `w` the first kernel ran with.  Otherwise (and
-// w = 4, 33 <= b <= 64, n >= 4096, enough rounds): that width up to round `plan_round`, then launches of
-// `plan_every` rounds each with TIERED widths (emd_lean_tiers_kernel; plan_widths: the widths of an
-// XCD's 8 cloud slots, heaviest first, 4 bits each).
-hipError_t emd_lean_launch(int b, int n, int w, const float *xyz1, float *dist, int *assignment, float eps,
-                           int iters, char *scratch, int fast_ok, int plan_round, int plan_every,
-                           unsigned long long plan_widths, int res_cap, hipStream_t stream) {
-  if (res_cap != 0 && n <= kResMaxN) {
-    // Clouds of at most kResMaxN points: the clustered rounds end as soon as at most |res_cap| persons are
-    // unassigned and the rest runs LDS-resident on one workgroup per cloud (emd_resident.h) -- res_cap > 0: on
-    // member 0 of the cloud's cluster at once, inside the same launch; res_cap < 0: in a launch of its own
-    // (every cloud waits for the last one to get there: A/B, and the fallback if the fused kernels do not fit).
-    const bool fused = res_cap > 0;
-    int cap = res_cap > 0 ? res_cap : -res_cap;
-    cap = cap > kResList ? kResList : cap;
-    hipError_t e = hipErrorUnknown;
-    if (fused) {
-      e = n <= 2048 ? emd_lean_launch_res<2048>(b, n, w, xyz1, dist, assignment, eps, iters, scratch, fast_ok, stream, cap)
-                    : emd_lean_launch_res<4096>(b, n, w, xyz1, dist, assignment, eps, iters, scratch, fast_ok, stream, cap);
-      if (e != hipSuccess) (void)hipGetLastError();
-    }
-    if (e != hipSuccess) e = emd_lean_launch_res<0>(b, n, w, xyz1, dist, assignment, eps, iters, scratch, fast_ok, stream, cap);
-    if (e != hipSuccess) return e;
-    // (fused: only clouds nobody finished -- none -- are left for it; it exits at once)
-    return emd_resident_launch(b, n, dist, assignment, eps, iters, scratch, stream);
-  }
-  int bpad = (b + 7) / 8 * 8;
-  const int c = bpad / 8;
-  // widths of an XCD's cloud slots: 0 = from the loads (the kernel), else the caller's, heaviest first, 4 bits each
-  unsigned long long pattern = c == 8 ? plan_widths : 0ull;
-  bool ok = true;
-  if (pattern != 0ull) {
-    int sum = 0;
-    for (int s = 0; s < c; ++s) {
-      const int ws = (int)((pattern >> (4 * s)) & 15ull);
-      ok = ok && (ws == 2 || ws == 3 || ws == 4 || ws == 5 || ws == 6 || ws == 8);
-      sum += ws;
-    }
-    ok = ok && sum == 4 * c;
-  }
-  // (below 4096 points a cloud has a few dozen bidders left at round 300: nothing to deal out -- measured: 2048 points +0.7 ms)
-  if (w == 4 && n >= 4096 && b >= 33 && b <= 64 && plan_every > 0 && ok && iters >= plan_round + 256) {
-    hipError_t e = emd_lean_launch_w<4>(b, n, xyz1, dist, assignment, eps, iters, scratch, fast_ok, plan_round, 1, stream);
-    for (int r = plan_round; e == hipSuccess && r < iters; r += plan_every) {
-      int stop = r + plan_every + 256 > iters ? iters : r + plan_every;   // (no short last launch)
-      int which = 2;
-      void *args[] = {&b, &bpad, &n, &xyz1, &dist, &assignment, &eps, &iters, &scratch, &fast_ok, &stop, &which, &pattern};
-#ifdef MVP_TEST_HOOKS
-      static const bool refuse = std::getenv("MVP_EMD_TIERS_FAIL") != nullptr;   // (libmvpops_hooks.so only: behave as if it did not fit)
-#else
-      constexpr bool refuse = false;
-#endif
-      e = refuse ? hipErrorCooperativeLaunchTooLarge
-                 : hipLaunchCooperativeKernel(reinterpret_cast<const void *>(emd_lean_tiers_kernel), dim3(4 * bpad),
-                                              dim3(kEmdThreads), args, 0, stream);
-      if (e != hipSuccess) {
-        // (the tiered kernel does not fit this device: the fixed-width kernel finishes what the first launch left)
-        (void)hipGetLastError();
-        return emd_lean_launch_w<4>(b, n, xyz1, dist, assignment, eps, iters, scratch, fast_ok, iters, 2, stream);
-      }
-      if (stop == iters) break;
-    }
-    return e;
-  }
-  if (w == 8) return emd_lean_launch_w<8>(b, n, xyz1, dist, assignment, eps, iters, scratch, fast_ok, iters, 1, stream);
-  if (w == 4) return emd_lean_launch_w<4>(b, n, xyz1, dist, assignment, eps, iters, scratch, fast_ok, iters, 1, stream);
-  if (w == 2) return emd_lean_launch_w<2>(b, n, xyz1, dist, assignment, eps, iters, scratch, fast_ok, iters, 1, stream);
-  return emd_lean_launch_w<1>(b, n, xyz1, dist, assignment, eps, iters, scratch, fast_ok, iters, 1, stream);
+#undef MVP_LEAN_KERNEL
+  return emd_launch_step(kernel, s, args, c.stream);
 }
 
 }  // namespace mvp

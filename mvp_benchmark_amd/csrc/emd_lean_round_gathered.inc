@@ -33,7 +33,7 @@
           GMT(2)   // [2] every member's word raised
           bool ok = !isb || ((unsigned)(g0 & 15ull) == T4 && (unsigned)(g1 & 7ull) == T6);
 #ifdef MVP_TEST_HOOKS
-          // MVP_EMD_POLL_DISTRUST=1 (fast_ok bit 2; libmvpops_hooks.so only): in rounds of odd eg the records that
+          // MVP_EMD_POLL_DISTRUST=1 (fast_ok's kFastPollDistrust; libmvpops_hooks.so only): in rounds of odd eg the records that
           // came with the words count as untagged, so that the re-read below stays tested
           if ((fast_ok & 4) != 0 && (eg & 1u) != 0) ok = !isb;
 #endif

@@ -11,17 +11,14 @@ __global__ __launch_bounds__(kEmdThreads) void emd_resident_kernel(
 }
 
 // Finishes the clouds emd_lean.hip's launch stopped for it (hand-over records with next_it != 0).
-hipError_t emd_resident_launch(int b, int n, float *dist, int *assignment, float eps, int iters, char *scratch,
-                               hipStream_t stream) {
-  if (n <= 2048)
-    hipLaunchKernelGGL(emd_resident_kernel<2048>, dim3(b), dim3(kEmdThreads), 0, stream, b, n, dist, assignment, eps,
-                       iters, scratch);
-  else if (n <= kResMaxN)
-    hipLaunchKernelGGL(emd_resident_kernel<4096>, dim3(b), dim3(kEmdThreads), 0, stream, b, n, dist, assignment, eps,
-                       iters, scratch);
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
+hipError_t emd_resident_launch(const EmdStep &s, EmdCall c) {
+  void *args[] = {&c.b, &c.n, &c.dist, &c.assignment, &c.eps, &c.iters, &c.scratch};
+  const void *kernel = nullptr;   // (no such instantiation: the launch fails)
+  switch (s.resn) {
+    case 2048: kernel = reinterpret_cast<const void *>(emd_resident_kernel<2048>); break;
+    case 4096: kernel = reinterpret_cast<const void *>(emd_resident_kernel<4096>); break;
+  }
+  return emd_launch_step(kernel, s, args, c.stream);
 }
 
 }  // namespace mvp

@@ -576,7 +576,8 @@ def test_emd_tiered_launch_refused_late_or_repeated_gives_the_same_bits():
     ) % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     outs = []
     # also: the plan made late (round 1500: clouds that collapsed to one workgroup are stopped and resumed), and made
-    # three times (rounds 600, 1300, 2000: the tiered launch itself stops and hands over to the next one)
+    # four times (PLAN_ROUND=600, PLAN_EVERY=700: the lean launch stops at round 600, then four tiered launches stop at
+    # rounds 1300, 2000, 2700 and 3000 -- each stops itself and hands over to the next one; tests/test_emd_plan_cpu.py case 10)
     # (MVP_EMD_SPLIT=2: the tiered launches; the default, 3, finishes clouds of this size LDS-resident -- last variant)
     for extra in ({"MVP_EMD_SPLIT": "2"}, {"MVP_EMD_SPLIT": "2", "MVP_EMD_TIERS_FAIL": "1"}, {"MVP_EMD_SPLIT": "2", "MVP_EMD_PLAN_ROUND": "1500"},
                   {"MVP_EMD_SPLIT": "2", "MVP_EMD_PLAN_ROUND": "600", "MVP_EMD_PLAN_EVERY": "700"}, {"MVP_EMD_SPLIT": "0"}, {}):
